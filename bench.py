@@ -14,6 +14,10 @@ the S.dot(H, .) of mlpconv.py:73. Inputs are resident in HBM before the timed re
               with the local SpMM over column chunks; total work fixed -> "strong" scaling.
 
 Run: python bench.py [--gpus N --steps K --warmup W]; N > 1 under torch.distributed.run.
+A plain run sets up, warms up, times the K steps and prints the headline line; `--full` adds
+every other measurement (roofline with live rocprofv3 passes, variants, dense kernels, the
+training step, CPU baselines, the N > 1 distributed block); `--dump-outputs DIR` writes the
+last timed step's Y (a fixed seeded row sample) as DIR/Y.npy.
 """
 from __future__ import annotations
 
@@ -698,11 +702,47 @@ def exchange_ab(H, rank, world, dev, part, Zl, K, B, eff, timed, reps, args, m) 
     return alt
 
 
+DUMP_BUDGET_BYTES = 48 * 2**20  # --dump-outputs: all ranks' files together stay below 64 MB
+
+
+def dump_outputs(out_dir: str, Y, K: int, rank: int, world: int) -> dict:
+    """--dump-outputs: what the timed path computed in its last step -- Y = H.Z, the array a
+    caller of gs.spmm / spmm_pipelined receives (this rank's rows at N > 1) -- as float32
+    `Y.npy` (`Y_rank<r>.npy` at N > 1). An output above the size budget is written as a fixed
+    sample of its rows: a sorted draw without replacement seeded by SEED + rank, so two builds
+    run with the same arguments write the same rows of the same product."""
+    n_rows = int(Y.shape[0])
+    keep = max(1, (DUMP_BUDGET_BYTES // world) // (4 * K))
+    name = "Y" if world == 1 else f"Y_rank{rank}"
+    if n_rows > keep:
+        rows = np.sort(np.random.default_rng(SEED + rank).choice(n_rows, size=keep, replace=False))
+        arr = Y[torch.from_numpy(rows).to(Y.device)]
+        what = f"rows sorted(default_rng({SEED + rank}).choice({n_rows}, {keep}, replace=False))"
+    else:
+        arr = Y
+        what = f"all {n_rows} rows"
+    arr = np.ascontiguousarray(arr.detach().to(torch.float32).cpu().numpy())
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {name: {"shape": list(arr.shape), "dtype": str(arr.dtype), "rows": what}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also measure everything else: the "
+                         "roofline record (live rocprofv3 passes at N = 1), the variants, the "
+                         "dense kernels, the training step, the CPU baselines, and at N > 1 the "
+                         "distributed block. Off by default: a plain run sets up, warms up, "
+                         "times --steps steps and prints the line. The --no-* switches below "
+                         "trim a --full run")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's result Y (a fixed seeded "
+                         "row sample when it is large) as float32 DIR/Y.npy "
+                         "(DIR/Y_rank<r>.npy at N > 1)")
     ap.add_argument("--config", default="twitter-world", choices=sorted(CONFIGS))
     ap.add_argument("--graph", default="powerlaw", choices=["powerlaw", "uniform"])
     ap.add_argument("--hidden", type=int, default=None, help="K (default: config hidden=300)")
@@ -748,6 +788,9 @@ def main():
     ap.add_argument("--partitioned", action="store_true",
                     help="use the row-partitioned (all-gather) path even at N = 1")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    full = args.full
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -763,11 +806,11 @@ def main():
     N, nnz = H.shape[0], H.nnz
     B = spmm_bytes(N, nnz, K)
 
-    # Live PMC (N = 1): the headline launch's HBM-side bytes, measured by rocprofv3 child
+    # Live PMC (--full, N = 1): the headline launch's HBM-side bytes, measured by rocprofv3 child
     # processes before this process touches the GPU (and for the uniform second run's graph).
     single = world == 1 and not args.partitioned
     live = live_u = H_u = None
-    if single and args.live_pmc and args.ld == 0 and args.steps > 0:
+    if full and single and args.live_pmc and args.ld == 0:
         if under_profiler():
             live = {"error": "skipped: this run is itself under rocprofv3"}
         else:
@@ -858,10 +901,14 @@ def main():
         elapsed = float(t.item())
     ms = elapsed / args.steps * 1e3
 
+    # the last timed step's result, before anything below launches into Y again
+    dumped = dump_outputs(args.dump_outputs, Y, K, rank, world) if args.dump_outputs else None
+
+    # Everything from here to the result line is --full's: a plain run has its headline already.
     # Live per-launch kernel time with HIP events on the SpMM's own stream. N = 1: the whole
     # graph; N > 1: this rank's local SpMM on the gathered operand (local algorithmic bytes).
     roofline = None
-    if args.steps > 0:
+    if full:
         if world == 1 and not args.partitioned:
             kstep, kbytes = None, B
             k_ms = ev0.elapsed_time(ev1) / args.steps
@@ -916,6 +963,7 @@ def main():
             roofline["scope"] = f"rank {rank} local SpMM ({part.n_local} rows, {part.nnz_local} nnz)"
 
     # N > 1 (or --partitioned): the two phases alone, max over ranks, for the comm fraction.
+    # `timed` and `reps` are defined without --full too: --exchange-ab (alternatives) uses them.
     dist_info = None
     if world > 1 or args.partitioned:
         def timed(fn, reps):
@@ -932,9 +980,10 @@ def main():
                 dt = float(tt.item())
             return dt
         reps = max(args.steps // 2, 1)
-        full = part.all_gather(Zl)
+    if full and (world > 1 or args.partitioned):
+        full_z = part.all_gather(Zl)
         t_comm = timed(lambda: part.all_gather(Zl), reps)
-        t_sp = timed(lambda: gs.spmm(part.A, full, out=Y, mode=eff, task_nnz=args.task_nnz), reps)
+        t_sp = timed(lambda: gs.spmm(part.A, full_z, out=Y, mode=eff, task_nnz=args.task_nnz), reps)
         gathered = part.exchange_bytes_per_row(K)
         import torch.distributed as dist
         dist_info = {"world_size": dist.get_world_size() if world > 1 else 1,
@@ -966,7 +1015,7 @@ def main():
         "value_kind": "edge-centric", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
         "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "edges_per_s": round(nnz / (ms * 1e-3)),
+        "full": full, "edges_per_s": round(nnz / (ms * 1e-3)),
         "config": {"workload": f"{cfg.name} H.Z SpMM fwd, {args.graph} degrees", "nodes": N,
                    "edges": cfg.n_edges, "nnz_H": nnz, "K": K, "mode": f"{args.mode}->{eff}",
                    "mode_resolution": ("the whole graph (RowPartitionedCSR.resolve_mode), the "
@@ -976,11 +1025,14 @@ def main():
                    "parallelism": f"row{world}" if world > 1 else "single",
                    "plan": info, "graph_gen_s": round(t_gen, 1)},
     }
+    if dumped:
+        rec["outputs"] = dumped
     if roofline:
         rec["roofline"] = roofline
     if dist_info:
         rec["distributed"] = dist_info
-    if world == 1 and not args.partitioned and args.variants:
+    extras = full and single  # the N = 1 extras below are --full's
+    if extras and args.variants:
         # SURVEY.md §8d second run: uniform degrees (no Infinity-Cache hub reuse)
         del Z, Y
         rec["variants"] = {"uniform": spmm_variant(cfg, "uniform", K, args.mode,
@@ -998,12 +1050,12 @@ def main():
             # `--mode fast` scaling series (the default series runs the whole graph's mode,
             # 'ordered', at every N: RowPartitionedCSR.resolve_mode)
             rec["variants"]["fast"] = spmm_mode_variant(A, H, K, "fast", max(args.steps, 5), dev)
-    if world == 1 and not args.partitioned and args.dense:
+    if extras and args.dense:
         rec["dense_kernels"] = dense_kernels_bench(max(args.steps // 2, 5), dev)
-    if world == 1 and not args.partitioned and args.train_step:
+    if extras and args.train_step:
         # BASELINE config 3: Twitter-US 2-layer fwd+bwd step (both layer-2 orders)
         rec["train_step"] = train_step_bench(max(args.steps // 2, 5), max(args.warmup, 2), dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         rec["cpu_baseline"] = scipy_baseline(H, K, args.cpu_budget)
         rec["cpu_port"] = cpu_baseline(H, K, args.cpu_budget / 5)
         try:

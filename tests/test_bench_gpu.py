@@ -29,8 +29,8 @@ def _json_line(out: str) -> dict:
 
 
 def test_bench_single_gpu_line(cuda):
-    r = subprocess.run([sys.executable, "bench.py", "--config", "geotext", "--steps", "3",
-                        "--warmup", "1", "--no-train-step", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--config", "geotext", "--steps",
+                        "3", "--warmup", "1", "--no-train-step", "--no-cpu-baseline"],
                        cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _json_line(r.stdout)
@@ -59,12 +59,52 @@ def test_bench_single_gpu_line(cuda):
     assert sum(v.get("math") == "bf16x6" for v in dk.values()) == 4  # NT x 2, TN, fused
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(cuda, tmp_path):
+    """A plain run times its steps and prints the headline line alone (the rest is --full's);
+    --dump-outputs writes the last timed step's Y: the product of the seeded graph and the
+    seeded operand, rebuilt here from the seeds alone and multiplied by the CPU oracle (bitwise
+    in the 'ordered' and 'rowwise' modes; 'fast' within the 1e-5 sparse.spmm documents)."""
+    import numpy as np
+    import torch
+
+    from graphconvgeo_amd.synth import CONFIGS, SEED, synthetic_graph
+    from oracle import gcn_oracle as O
+
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--config", "geotext",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                       cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = _json_line(r.stdout)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus",
+                "steps", "warmup", "config"):
+        assert key in rec, key
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["full"] is False
+    assert rec["unit"] == "GB/s" and rec["dtype"] == "f32" and rec["higher_is_better"] is True
+    assert rec["ms_per_step"] > 0 and rec["value"] > 0
+    for key in ("roofline", "variants", "dense_kernels", "train_step", "cpu_baseline", "cpu_port",
+                "cpu_multicore", "distributed"):
+        assert key not in rec, key
+    assert os.listdir(tmp_path / "out") == ["Y.npy"]
+    Y = np.load(tmp_path / "out" / "Y.npy")
+    cfg = CONFIGS["geotext"]
+    n, k = cfg.n_nodes, cfg.hidden
+    assert Y.dtype == np.float32 and Y.shape == (n, k) == tuple(rec["outputs"]["Y"]["shape"])
+    H = synthetic_graph(cfg.n_nodes, cfg.n_edges)
+    g = torch.Generator(device=cuda).manual_seed(SEED)
+    Z = torch.randn((n, k), generator=g, device=cuda, dtype=torch.float32).cpu().numpy()
+    ref = O.spmm_f32(H, Z)
+    if rec["config"]["mode"].endswith("->fast"):
+        assert np.abs(Y - ref).max() <= 1e-5
+    else:
+        assert np.array_equal(Y, ref)
+
+
 def test_bench_two_ranks_gloo(cuda):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",
            "--gpus", "2", "--config", "twitter-us", "--steps", "3", "--warmup", "1",
-           "--dist-backend", "gloo", "--exchange-ab"]
+           "--dist-backend", "gloo", "--full", "--exchange-ab"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _json_line(r.stdout)

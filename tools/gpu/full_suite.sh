@@ -1,5 +1,5 @@
 #!/bin/bash
-# Whole -m gpu suite, smoke(), then the default bench line (what the driver runs at round end).
+# Whole -m gpu suite, smoke(), the plain bench line, then the --full one (what the driver runs).
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/full
@@ -11,3 +11,6 @@ tail -1 $out/smoke.log
 timeout -k 10 400 python -u bench.py > $out/bench.log 2>&1 || { tail -30 $out/bench.log; exit 1; }
 grep '^{' $out/bench.log > $out/bench.json
 cut -c1-600 $out/bench.json
+timeout -k 10 600 python -u bench.py --full > $out/bench_full.log 2>&1 || { tail -30 $out/bench_full.log; exit 1; }
+grep '^{' $out/bench_full.log > $out/bench_full.json
+cut -c1-600 $out/bench_full.json
