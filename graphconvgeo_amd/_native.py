@@ -50,6 +50,13 @@ SIGNATURES = {
                                                 C.c_int, _p, _i64, _p, C.c_size_t, _p, _p]),
     "gcg_relu_backward_gate_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p,
                                              C.c_size_t, _p]),
+    "gcg_dropout_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _i64, C.c_uint32, C.c_float,
+                                  C.c_uint64, _p, C.c_uint32, _i64, _p, _p]),
+    "gcg_dropout_relu_backward_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p,
+                                                C.c_size_t, C.c_uint32, C.c_float, C.c_uint64,
+                                                _p, C.c_uint32, _i64, _p]),
+    "gcg_csr_dropout_f32": (C.c_int, [_i64, _i64, _i64, _p, _p, _p, _p, C.c_int, C.c_uint32,
+                                      C.c_float, C.c_uint64, _p, C.c_uint32, _p]),
     "gcg_spmm_plan_host": (C.c_int, [_i64, _p, _p, _i64, _i64, C.c_int, _p, _i64, _pi64, _p,
                                      _i64, _pi64, _pi64]),
     "gcg_adam_step_f32": (C.c_int, [_i64, _p, _p, _p, _p, _p, C.c_float, C.c_float, C.c_float,

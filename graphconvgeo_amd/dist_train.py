@@ -389,7 +389,9 @@ class RowPartitionedMLPCONV:
         if dtype != "float32":
             raise ValueError("the GPU path computes in float32 (mlpconv.py dtype='float32')")
         if drop_out:
-            raise NotImplementedError("dropout is out of scope (main_mlpconv uses drop_out=False)")
+            raise NotImplementedError("dropout is not built into the row-partitioned trainer; "
+                                      "the single-GPU MLPCONV(drop_out=True) has it "
+                                      "(graphconvgeo_amd.dropout)")
         if complete_prob:
             raise NotImplementedError("complete_prob (soft labels) is not on the graded path")
         if loss_name != "log":

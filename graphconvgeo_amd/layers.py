@@ -38,6 +38,7 @@ import torch
 import torch.nn as nn
 
 from . import dense
+from . import dropout as _drop
 from . import ops as _ops  # registers torch.ops.gcg.* (the compiled path)
 from . import sparse as gs
 
@@ -110,10 +111,12 @@ def _as_device_csr(m, device) -> gs.DeviceCSR:
 
 
 class _CSRMatMul(torch.autograd.Function):
-    """Y = act(A . Z + bias)[rows]; differentiable in Z and bias (S.dot + epilogue)."""
+    """Y = act(A . Z + bias)[rows]; differentiable in Z and bias (S.dot + epilogue).
+    drop (a dropout.DropoutSpec): Y = drop(act(...)), the mask keyed on Y's own (row, column)
+    positions; its backward regenerates the mask inside the rectify-backward pass."""
 
     @staticmethod
-    def forward(ctx, Z, bias, A: gs.DeviceCSR, act, rows, mode):
+    def forward(ctx, Z, bias, A: gs.DeviceCSR, act, rows, mode, drop=None):
         gate = None
         if act == "relu" and any(ctx.needs_input_grad[:2]):
             # rectify gate (2/1/0 for pre-activation > 0, == 0, < 0) written by the SpMM
@@ -123,6 +126,9 @@ class _CSRMatMul(torch.autograd.Function):
             n_out = A.n_rows if rows is None else len(rows)
             gate = gs.empty_gate(n_out, Z.shape[1], A.device)
         Y = gs.spmm(A, Z, bias=bias, act=act, rows=rows, mode=mode, gate=gate)
+        if drop is not None:
+            _drop.dropout_dense(Y, drop, out=Y)  # in place (gcg_dropout_f32)
+        ctx.drop = drop
         ctx.A, ctx.act, ctx.rows, ctx.mode = A, act, rows, mode
         ctx.has_bias = bias is not None
         ctx.save_for_backward(gate)
@@ -133,7 +139,12 @@ class _CSRMatMul(torch.autograd.Function):
         A, rows = ctx.A, ctx.rows
         (gate,) = ctx.saved_tensors
         want_bias = ctx.has_bias and ctx.needs_input_grad[1]
-        if gate is not None and gY.shape[1] <= 1024:
+        if ctx.drop is not None:
+            # the mask regenerated, Theano's rectify gradient and the bias gradient in one
+            # pass (gcg_dropout_relu_backward_f32; gate None: no rectify)
+            g, g_bias = _drop.dropout_relu_backward(gY, ctx.drop, gate=gate,
+                                                    bias_grad=want_bias)
+        elif gate is not None and gY.shape[1] <= 1024:
             # Theano rectify gradient and bias gradient in one pass (gcg_relu_backward_gate_f32)
             g, g_bias = gs.relu_backward(gY.contiguous() if gY.stride(-1) != 1 else gY,
                                          gate=gate, bias_grad=want_bias)
@@ -156,7 +167,7 @@ class _CSRMatMul(torch.autograd.Function):
                               mode=ctx.mode)
             else:
                 g_Z = A.tmatmul(g if g.stride(-1) == 1 else g.contiguous(), mode=ctx.mode)
-        return g_Z, g_bias, None, None, None, None
+        return g_Z, g_bias, None, None, None, None, None
 
 
 def _index_csr_cached(rows: gs.RowSelection, n_rows: int):
@@ -168,11 +179,17 @@ def _index_csr_cached(rows: gs.RowSelection, n_rows: int):
 
 def csr_matmul(A: gs.DeviceCSR, Z: torch.Tensor, bias: Optional[torch.Tensor] = None,
                act: Optional[str] = None, rows: Optional[gs.RowSelection] = None,
-               mode: str = "auto") -> torch.Tensor:
+               mode: str = "auto", dropout: Optional["_drop.DropoutSpec"] = None) -> torch.Tensor:
     """Differentiable S.dot(A, Z) (+ bias, rectify, row subset) through the HIP kernels.
     Under torch.compile the registered op gcg::spmm_csr (graphconvgeo_amd.ops: same kernels,
     a fake kernel for tracing, its autograd formula made of gcg ops) stands in for the
-    autograd.Function."""
+    autograd.Function. dropout: a dropout.DropoutSpec masks the output (eager only, at most
+    1024 columns: the fused backward's limit)."""
+    if dropout is not None:
+        _drop._not_under_compile()
+        if Z.shape[1] > 1024:
+            raise NotImplementedError("output dropout takes at most 1024 columns")
+        return _CSRMatMul.apply(Z, bias, A, act, rows, mode, dropout)
     if torch.compiler.is_compiling():
         return _ops.spmm_csr(A, Z, bias, act, rows, mode)
     return _CSRMatMul.apply(Z, bias, A, act, rows, mode)
@@ -202,12 +219,20 @@ class GraphConvLayer(nn.Module):
 
     input: sparse (scipy / DeviceCSR; X . W runs in the HIP SpMM) or dense torch tensor
     (X . W is an fp32 GEMM). H: scipy sparse or DeviceCSR, uploaded once and shared.
+
+    dropout > 0: lasagne.layers.dropout on the layer's output (mlpconv.py:210-211), unless
+    forward(..., deterministic=True): one in-place masked pass after the SpMM, its backward
+    fused into the rectify backward (graphconvgeo_amd.dropout). The mask is keyed on the
+    output's (row, column) positions. dropout_stream: a dropout.DropoutStream; None draws a
+    seed after W, as Lasagne's DropoutLayer constructed after the DenseLayer does.
     """
 
     def __init__(self, incoming=None, H=None, num_units: int = None, W=None, b=0.0,
                  nonlinearity="rectify", device: Union[str, torch.device] = "cuda",
                  mode: str = "auto", require_sparse_input: bool = False, rng=None,
-                 in_features: Optional[int] = None):
+                 in_features: Optional[int] = None, dropout: float = 0.0,
+                 dropout_stream: Optional["_drop.DropoutStream"] = None,
+                 dropout_rescale: bool = True):
         super().__init__()
         if num_units is None:
             raise ValueError("num_units is required")
@@ -230,11 +255,23 @@ class GraphConvLayer(nn.Module):
         self.mode = mode
         self.require_sparse_input = require_sparse_input
         self._sparse_inputs = {}
+        self.dropout = float(dropout)
+        self.dropout_rescale = bool(dropout_rescale)
+        _drop.dropout_threshold(self.dropout)
+        if self.dropout > 0.0 and dropout_stream is None:
+            dropout_stream = _drop.DropoutStream(_drop.draw_seed(rng), 1, self.device)
+        self.dropout_stream = dropout_stream
 
     def _sparse_input(self, x) -> gs.DeviceCSR:
         return _upload_cached(self._sparse_inputs, x, self.device)
 
-    def forward(self, input, target_indices=None, **kwargs):
+    def _dropout_spec(self, deterministic: bool):
+        if self.dropout == 0.0:
+            return None
+        return _drop.make_spec(self.dropout_stream, self.dropout, self.dropout_rescale,
+                               deterministic)
+
+    def forward(self, input, target_indices=None, deterministic: bool = False, **kwargs):
         is_sparse = isinstance(input, gs.DeviceCSR) or sps.issparse(input)
         if self.require_sparse_input and not is_sparse:
             raise ValueError("Input for this layer must be sparse")  # mlpconv.py:67-69
@@ -246,6 +283,12 @@ class GraphConvLayer(nn.Module):
         if target_indices is not None:
             rows = target_indices if isinstance(target_indices, gs.RowSelection) else \
                 gs.RowSelection(target_indices, self.device)
+        drop = self._dropout_spec(deterministic)
+        if drop is not None:
+            if self.post is not None:
+                raise NotImplementedError("output dropout needs a fused nonlinearity (rectify "
+                                          "or linear): the mask is applied to the SpMM output")
+            return csr_matmul(self.H, Z, self.b, self.fused_act, rows, self.mode, dropout=drop)
         Y = csr_matmul(self.H, Z, self.b, self.fused_act, rows, self.mode)
         return self.post(Y) if self.post is not None else Y
 
@@ -350,8 +393,13 @@ class ConvolutionDenseLayer(GraphConvLayer):
                 gs.RowSelection(target_indices, self.device)
         return csr_matmul(self.H, input, None, None, rows, self.mode)
 
-    def forward(self, input, target_indices=None, **kwargs):
+    def forward(self, input, target_indices=None, deterministic: bool = False, **kwargs):
         sparse_in = isinstance(input, gs.DeviceCSR) or sps.issparse(input)
+        if self._dropout_spec(deterministic) is not None and not (
+                self.order == "reference" and self.fused_act is not None):
+            # only GraphConvLayer.forward's generic path carries the mask
+            raise NotImplementedError("output dropout on ConvolutionDenseLayer needs "
+                                      "order='reference' and a fused nonlinearity")
         if (self.order == "reference" and not sparse_in and REASSOCIATED_BACKWARD
                 and self.fused_act is None and self.num_units > self.num_inputs
                 and torch.is_grad_enabled()):
@@ -367,7 +415,8 @@ class ConvolutionDenseLayer(GraphConvLayer):
             Y = _TransformPropagate.apply(input, Wa, self.b, self.H, rows, self.mode, slot, proj)
             return self.post(Y) if self.post is not None else Y
         if self.order == "reference" or sparse_in:
-            return super().forward(input, target_indices=target_indices, **kwargs)
+            return super().forward(input, target_indices=target_indices,
+                                   deterministic=deterministic, **kwargs)
         P = self.propagate(input, target_indices)  # (H . h)[rows], K wide
         Y = dense.matmul(P, self.W, self.b)
         if self.fused_act == "relu":

@@ -18,8 +18,11 @@ step over all N nodes (mlpconv.py:293-295):
 Validation every 10 epochs on dev, best-params restore and early stopping as
 mlpconv.py:296-318. The checkpoint is `torch.save` of the best parameters when
 `model_file` is given (the reference pickles to ./data/..., mlpconv.py:310-313).
-Dropout (drop_out=True) is out of scope: main_mlpconv runs with drop_out=False
-(tensormain.py:233).
+drop_out=True (mlpconv.py:155, 199-201, 210-211; main_mlpconv itself runs with drop_out=False,
+tensormain.py:233): `drop_out_hid, drop_out_in = dropout_coefs`; SparseInputDropoutLayer on X,
+then lasagne.layers.dropout on the hidden layer, both with counter-based Philox masks that no
+kernel stores (graphconvgeo_amd.dropout): training steps draw a new mask per epoch, validation,
+the final dev evaluation and predict* run deterministic.
 """
 from __future__ import annotations
 
@@ -35,6 +38,7 @@ from . import dense
 from . import sparse as gs
 from ._native import call
 from .sparse import _ptr, _stream_handle
+from .dropout import DropoutStream, SparseInputDropoutLayer, draw_seed
 from .layers import ConvolutionDenseLayer, SparseConvolutionDenseLayer
 
 log = logging.getLogger(__name__)
@@ -121,8 +125,12 @@ class MLPCONV:
                  order: str = "auto", use_graph: bool = False):
         if dtype != "float32":
             raise ValueError("the GPU path computes in float32 (mlpconv.py dtype='float32')")
-        if drop_out:
-            raise NotImplementedError("dropout is out of scope (main_mlpconv uses drop_out=False)")
+        self.drop_out = bool(drop_out)
+        if self.drop_out:
+            drop_out_hid, drop_out_in = dropout_coefs  # mlpconv.py:155
+            for p in (drop_out_hid, drop_out_in):
+                if not 0.0 <= float(p) < 1.0:
+                    raise ValueError("dropout_coefs must be in [0, 1)")
         if complete_prob:
             raise NotImplementedError("complete_prob (soft labels) is not on the graded path")
         if loss_name != "log":
@@ -166,9 +174,22 @@ class MLPCONV:
         W1 = W2 = None
         if self.init_parameters is not None:
             W1, _b1, W2, _b2 = self.init_parameters
+        # drop_out: the layers in the reference's construction order, each dropout layer drawing
+        # its seed from the weights' stream as Lasagne's DropoutLayer.__init__ does (also when
+        # init_parameters supplies the weights): input-dropout seed, W1, hidden-dropout seed, W2.
+        # [recalled Lasagne 0.2, unpinned]. drop_out=False draws nothing extra.
+        p_hid, p_in = self.dropout_coefs if self.drop_out else (0.0, 0.0)
+        self.l_in_drop = None
+        if self.drop_out:
+            self.l_in_drop = SparseInputDropoutLayer(in_size, p=p_in, device=self.device, rng=rng,
+                                                     stream_id=0)
         self.l_hid1 = SparseConvolutionDenseLayer(in_size, H=Hd, num_units=self.hidden_layer_size,
                                                   W=W1, nonlinearity="rectify", device=self.device,
-                                                  mode=self.mode, rng=rng)
+                                                  mode=self.mode, rng=rng, dropout=p_hid)
+        if self.drop_out and self.l_hid1.dropout_stream is None:  # p_hid == 0: still drawn
+            self.l_hid1.dropout_stream = DropoutStream(draw_seed(rng), 1, self.device)
+        self.dropout_streams = [] if not self.drop_out else \
+            [self.l_in_drop.stream, self.l_hid1.dropout_stream]
         self.l_out = ConvolutionDenseLayer(self.l_hid1, H=self.l_hid1.H, num_units=out_size,
                                            W=W2, nonlinearity=None, device=self.device,
                                            mode=self.mode, rng=rng,
@@ -185,12 +206,20 @@ class MLPCONV:
         return self.l_out.order == "propagate_first" and \
             self.l_out.num_units <= dense.FUSED_MAX_COLS
 
+    def _hidden(self, deterministic: bool = True) -> torch.Tensor:
+        """The hidden layer's output; with drop_out and not deterministic, behind this step's
+        input and hidden masks."""
+        if not self.drop_out:
+            return self.l_hid1(self.Xd)
+        X = self.Xd if deterministic else self.l_in_drop(self.Xd)
+        return self.l_hid1(X, deterministic=deterministic)
+
     def _logits(self, rows: gs.RowSelection) -> torch.Tensor:
-        h = self.l_hid1(self.Xd)
+        h = self._hidden()
         return self.l_out(h, target_indices=rows)  # (H.(h.W2) + b2)[rows], pre-softmax
 
     def _probabilities(self, rows: gs.RowSelection) -> torch.Tensor:
-        h = self.l_hid1(self.Xd)
+        h = self._hidden()
         if self._fused_output():
             return self._proj.probabilities(self.l_out.propagate(h, rows), self.l_out.W,
                                             self.l_out.b)
@@ -202,10 +231,12 @@ class MLPCONV:
         return dense.l1l2_penalty([self.l_out.W, self.l_hid1.W],
                                   [(c_out * 0.5, c_out * 0.5), (c_hid * 0.5, c_hid * 0.5)])
 
-    def _loss_acc(self, rows: gs.RowSelection, y: torch.Tensor, penalty: bool = True):
+    def _loss_acc(self, rows: gs.RowSelection, y: torch.Tensor, penalty: bool = True,
+                  deterministic: bool = True):
         """categorical_crossentropy(softmax(logits), y).mean() (+ penalty) and the argmax
-        accuracy (mlpconv.py:227-253), through the HIP softmax-CE kernels."""
-        h = self.l_hid1(self.Xd)
+        accuracy (mlpconv.py:227-253), through the HIP softmax-CE kernels. deterministic=False
+        (the training step, mlpconv.py:223 vs 246): with this step's dropout masks."""
+        h = self._hidden(deterministic)
         T, w = len(rows), None
         d = rows.distinct() if self.distinct_targets else None
         if d is not None:
@@ -300,9 +331,13 @@ class MLPCONV:
         Adam state are restored, so the graph path computes exactly the eager trajectory."""
         rows = self.rows["train"]
 
+        streams = self.dropout_streams
+
         def eager():
+            for s in streams:  # host half of the masks: this epoch's step value
+                s.advance()
             opt.zero_grad()
-            loss, acc = self._loss_acc(rows, y_train)
+            loss, acc = self._loss_acc(rows, y_train, deterministic=False)
             loss.backward()
             opt.step()
             return loss.detach(), acc
@@ -311,6 +346,7 @@ class MLPCONV:
             return eager
         snap_p = [p.detach().clone() for p in self.params]
         snap_o = opt.state()
+        snap_s = [s.step for s in streams]
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
@@ -320,12 +356,14 @@ class MLPCONV:
             for p, s in zip(self.params, snap_p):
                 p.copy_(s)
         opt.load_state(snap_o)
+        for s, step in zip(streams, snap_s):  # the warm-up's mask step is not a training step
+            s.set_step(step)
         opt.zero_grad()
         graph = torch.cuda.CUDAGraph()
         opt.prepare()  # step 1's a_t, written before capture (and before every replay)
         opt.t -= 1
         with torch.cuda.graph(graph):
-            loss, acc = self._loss_acc(rows, y_train)
+            loss, acc = self._loss_acc(rows, y_train, deterministic=False)
             loss.backward()
             opt.apply()
         static = (loss.detach(), acc)
@@ -333,6 +371,8 @@ class MLPCONV:
 
         def replay():
             opt.prepare()
+            for s in streams:
+                s.advance()
             graph.replay()
             # the replay's Adam update moved W2 in place without bumping its version counter:
             # eager calls (validation, predict) must re-copy the padded weight copies

@@ -532,6 +532,12 @@ class DeviceCSR:
         out.index_copy_(0, cols, head)
         return out
 
+    def dropout_view(self, stream):
+        """This matrix behind the dropout mask of `stream` (graphconvgeo_amd.dropout.DropoutView,
+        cached per stream): same structure, plans and hints, its own values buffer."""
+        from .dropout import dropout_view
+        return dropout_view(self, stream)
+
     def __repr__(self):
         return f"DeviceCSR(shape={self.shape}, nnz={self.nnz}, device={self.device})"
 

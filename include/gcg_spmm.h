@@ -233,6 +233,54 @@ gcg_status gcg_relu_backward_gate_f32(int64_t M, int64_t K, const float* gY, int
                                       gcg_stream_t stream);
 
 /*
+ * Dropout (lasagne.layers.DropoutLayer and the reference's SparseInputDropoutLayer,
+ * mlpconv.py:37-58, 199-201, 210-211) with a counter-based mask: no mask is stored, every
+ * kernel that needs the decision of an element recomputes it from the element's coordinates.
+ * Element (i, j) (logical row, logical column) is kept iff
+ *     philox4x32_10(counter = (uint32 i, uint32 (j >> 2), uint32 *step_dev, stream_id),
+ *                   key = (seed & 0xffffffff, seed >> 32))[j & 3] >= threshold
+ * (Philox4x32-10 of Random123: multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 /
+ * 0xBB67AE85). threshold = floor(p * 2^32) and scale = 1 / (1 - p) (or 1: rescale off) are
+ * computed by the caller. A kept element is fl32(v * scale); a dropped one is written as +0.0
+ * (never v * 0: NaN / Inf do not pass a dropped slot). *step_dev is a device int32 read by the
+ * kernel, so a captured HIP graph draws a new mask on every replay (the convention of
+ * gcg_adam_step_f32). All three calls validate on the host, allocate nothing, and return
+ * GCG_OK without a launch on an empty problem.
+ *
+ * gcg_dropout_f32: Y[r][c] = drop(X[r][c]) for an M x K block whose logical rows are
+ * row0 + r and logical columns col_ids ? col_ids[c] : c (col_ids: K device int32, for a block
+ * of gathered columns). Y may alias X. Columns >= K of a padded row are never written.
+ *
+ * gcg_dropout_relu_backward_f32: the backward of drop(rectify(.)) in one pass:
+ * t = keep ? fl32(gY * scale) : 0, g = t, t/2, 0 for gate byte 2, 1, 0 (as
+ * gcg_relu_backward_gate_f32; gate NULL: g = t), bias_grad = column sums of g (nullable).
+ * Same row blocks, partial layout, workspace size (gcg_relu_backward_f32_workspace_bytes) and
+ * final reduction as gcg_relu_backward_gate_f32: bitwise what that call gives on the
+ * pre-masked gradient. g_out may alias gY. K <= 1024.
+ *
+ * gcg_csr_dropout_f32: vals_out[k] = drop(vals[k]) for every stored entry of a CSR, structure
+ * untouched (dropped entries stay as explicit zeros). transposed = 1: the arrays are CSR(X^T),
+ * an entry in storage row r with index c is the logical element (i, j) = (c, r), so X and X^T
+ * drop the same elements. vals_out may alias vals. Work is split by nonzeros, not rows.
+ */
+gcg_status gcg_dropout_f32(int64_t M, int64_t K, const float* X, int64_t ldx, float* Y,
+                           int64_t ldy, uint32_t threshold, float scale, uint64_t seed,
+                           const int32_t* step_dev, uint32_t stream_id, int64_t row0,
+                           const int32_t* col_ids /*nullable*/, gcg_stream_t stream);
+gcg_status gcg_dropout_relu_backward_f32(int64_t M, int64_t K, const float* gY, int64_t ldg,
+                                         const uint8_t* gate /*nullable*/, int64_t ldgate,
+                                         float* g_out, int64_t ldo,
+                                         float* bias_grad /*nullable*/, void* workspace,
+                                         size_t workspace_bytes, uint32_t threshold, float scale,
+                                         uint64_t seed, const int32_t* step_dev,
+                                         uint32_t stream_id, int64_t row0, gcg_stream_t stream);
+gcg_status gcg_csr_dropout_f32(int64_t n_rows, int64_t n_cols, int64_t nnz,
+                               const int32_t* indptr, const int32_t* indices, const float* vals,
+                               float* vals_out, int transposed, uint32_t threshold, float scale,
+                               uint64_t seed, const int32_t* step_dev, uint32_t stream_id,
+                               gcg_stream_t stream);
+
+/*
  * Column sums out[c] = sum_r X[r][c] (the bias gradient of a dense projection, colsum of the
  * logits gradient; Theano's grad of T.dot(h, W) + b, mlpconv.py:88-93), deterministic, same
  * kernels and workspace (gcg_relu_backward_f32_workspace_bytes) as gcg_relu_backward_f32.

@@ -58,6 +58,8 @@ def main():
     ap.add_argument("--theano-backward", action="store_true",
                     help="reference order: autograd in Theano's association "
                          "(layers.REASSOCIATED_BACKWARD off)")
+    ap.add_argument("--dropout", type=float, nargs=2, default=None, metavar=("P_HID", "P_IN"),
+                    help="time the step with drop_out=True, dropout_coefs=[P_HID, P_IN]")
     args = ap.parse_args()
     gs.WIDE_ROW_ALIGN = not args.legacy_stride
     if args.theano_backward:
@@ -95,7 +97,8 @@ def main():
     test_idx = np.arange(int(0.8 * n), n, dtype=np.int32)
 
     clf = MLPCONV(n_epochs=0, hidden_layer_size=cfg.hidden, device=dev, seed=1, mode=args.mode,
-                  order=args.order, use_graph=args.graph)
+                  order=args.order, use_graph=args.graph, drop_out=args.dropout is not None,
+                  dropout_coefs=args.dropout or (0.5, 0.5))
     clf.fit(X, train, dev_idx, test_idx, Y, H)  # builds layers, uploads H/X, no epochs
     y_train = torch.as_tensor(Y[train].astype(np.int32), device=dev)
     opt = LasagneAdam(clf.params)
@@ -105,11 +108,17 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
+    # mean over the timed steps (host clock, one sync) and the median of the per-step times
+    # between device events recorded on the stream (no extra sync inside the loop)
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    marks[0].record()
+    for i in range(args.steps):
         step()
+        marks[i + 1].record()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / args.steps * 1e3
+    per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     K, C = cfg.hidden, cfg.n_classes
     nnzH, nnzX = H.nnz, X.nnz
     # SpMMs per step: X.W1, H.Z1, H.Z2 (train rows only), H.g2, H.g1, X^T.g; the layer-2
@@ -124,6 +133,8 @@ def main():
     sp_fwd_rows = spmm_bytes(len(uniq), nnz_t, width2)
     total = sp + sp_fwd_rows
     rec = {"metric": "GCN 2-layer fwd+bwd+adam step", "config": cfg.name, "ms_per_step": round(ms, 3),
+           "median_ms_per_step": round(float(np.median(per_step)), 3) if per_step else None,
+           "dropout": args.dropout,
            "nodes": n, "nnz_H": nnzH, "nnz_X": nnzX, "F": cfg.n_features, "K": K, "C": C,
            "train_rows": len(train), "train_rows_distinct": int(uniq.size),
            "spmm_algorithmic_bytes_per_step": total,
