@@ -10,7 +10,10 @@ Product modules (all compute runs in libgcg_spmm.so HIP kernels; no CPU fallback
   graph        H = D^-1/2 (A+I) D^-1/2 construction, host (scipy) and device (HIP)
   mentions     mention-graph parsing (host) and projection (HIP), data.py:226-375
   mlpconv      MLPCONV trainer (mlpconv.py:121-352) on the GPU
+  mlp          MLP mini-batch trainer (mlp.py:96-311) on the GPU, input_convolution (H * X)
   synth        seeded synthetic graphs / features for the BASELINE configs
+
+`MLP`, `input_convolution` and `DeviceCSR` are imported lazily from the package itself.
 """
 import os as _os
 
@@ -25,4 +28,14 @@ __version__ = "0.1.0"
 _os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "8")
 
 __all__ = ["sparse", "ops", "layers", "dense", "distributed", "dist_train", "graph", "mentions",
-           "mlpconv", "synth"]
+           "mlpconv", "mlp", "synth", "MLP", "input_convolution", "DeviceCSR"]
+
+_LAZY = {"MLP": "mlp", "input_convolution": "mlp", "DeviceCSR": "sparse"}
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        import importlib
+
+        return getattr(importlib.import_module("." + _LAZY[name], __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,456 @@
+"""MLP -- the reference's mini-batch trainer (mlp.py:96-311) with every product on the GPU.
+
+The model tensormain.main_justinputconv trains (tensormain.py:79-150): the features are
+pre-multiplied once, X_conv = H * X (`input_convolution`, the HIP SpGEMM), then a sparse-input
+MLP -- rectify(X.W1 + b1) (SparseInputDenseLayer), softmax(h.W2 + b2) -- is trained on
+shuffled mini-batches (mlp.py:77-92, 268-270) with lasagne.updates.adam(lr=0.002) (mlp.py:244).
+
+One epoch:
+  order     np.random.shuffle(np.arange(n)) from numpy's global stream; batches are
+            order[s:s+B] for s in range(0, n-B+1, B), the tail is dropped (mlp.py:81-91)
+  segment   the column grouping of all the epoch's batches at once, on the device
+            (gcg_minibatch_segment): per batch the touched columns of X[batch] and, per column,
+            the (row position, value) entries -- (X[batch])^T without building it per step
+  step      h = rectify(X[batch].W1 + b1) with gate bytes (plan-less HIP SpMM over the batch's
+            rows), the fused MFMA output layer + loss and its gradients (dense), the rectify
+            backward + db1 (one pass), then ONE pass over W1 (gcg_minibatch_w1_step_f32): the
+            data gradient of the rows the batch touches, the L1/L2 penalty gradient and Adam,
+            with no F x K gradient in memory; b1, W2, b2 through gcg_adam_step_f32.
+No host synchronisation happens between the first and the last batch of an epoch.
+
+Validation: the reference runs f_val on dev after every batch and uses the last one of the
+epoch (mlp.py:271-280); here it runs once per epoch, after the last batch. Model selection is
+mlp.py:272-285: strict acc_val > best_val_acc keeps the parameters, otherwise a counter runs up
+to early_stopping_max_down; the best parameters are restored (the last ones when no epoch ever
+improved -- the reference would crash on None there).
+
+Left out, as MLPCONV leaves them: complete_prob (soft labels), drop_out, dense inputs.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import logging
+
+import numpy as np
+import scipy.sparse as sps
+import torch
+from torch.autograd.graph import increment_version
+
+from . import dense
+from . import sparse as gs
+from ._native import GCG_ACT_NONE, GCG_ACT_RELU, call
+from .layers import _as_device_csr, _as_tensor, _glorot_uniform, _upload_cached
+from .mlpconv import LasagneAdam
+from .sparse import _ptr, _stream_handle
+
+log = logging.getLogger(__name__)
+
+# Entries (selected nonzeros) segmented per gcg_minibatch_segment call: an epoch with more is cut
+# into runs of whole batches (the sizes come from the host's copy of indptr, so a run boundary
+# costs no synchronisation). 2^26 entries need ~2.2 GB of keys, payloads and outputs.
+SEGMENT_CHUNK_ENTRIES = 1 << 26
+
+
+def iterate_minibatch_indices(n: int, batchsize: int, shuffle: bool = True):
+    """The index lists of mlp.py:81-91 (iterate_minibatches): one np.random.shuffle of
+    arange(n) from numpy's global stream, then order[s:s+B] for s in range(0, n-B+1, B); the
+    tail is dropped. Returns the list of batches."""
+    order = np.arange(n)
+    if shuffle:
+        np.random.shuffle(order)
+    return [order[s:s + batchsize] for s in range(0, n - batchsize + 1, batchsize)]
+
+
+def n_batches(n: int, batchsize: int) -> int:
+    if batchsize <= 0:
+        raise ValueError("batch_size must be positive")
+    if n < batchsize:
+        raise ValueError(f"{n} training rows are fewer than one batch of {batchsize}")
+    return (n - batchsize) // batchsize + 1
+
+
+def output_size(Y_train) -> int:
+    """out_size = len(set(Y_train)) (mlp.py:132) -- the number of distinct labels, not max+1."""
+    return len(set(np.asarray(Y_train).tolist()))
+
+
+def default_hidden_size(out_size: int, in_size: int) -> int:
+    """mlp.py:138."""
+    return min(5 * out_size, int(in_size / 20))
+
+
+def input_convolution(H, X, device="cuda") -> gs.DeviceCSR:
+    """X_conv = H * X, then .tocsr().astype('float32') (tensormain.py:114-115), on the GPU
+    (sparse.spgemm: every entry summed in scipy's order, canonical output). A float64 scipy H --
+    the reference's D^-1/2 A D^-1/2 is float64 there -- accumulates in float64 as scipy's
+    upcast does; a float32 H or a DeviceCSR in float32."""
+    Xd = _as_device_csr(X, device)
+    if isinstance(H, gs.DeviceCSR):
+        return gs.spgemm(H, Xd)
+    if not sps.issparse(H):
+        raise ValueError("Input for this layer must be sparse")
+    Hc = H.tocsr()
+    if Hc.dtype == np.float64:
+        Hd = gs.DeviceCSR.from_scipy(Hc.astype(np.float32), Xd.device)
+        return gs.spgemm(Hd, Xd, a_data64=torch.from_numpy(np.ascontiguousarray(Hc.data))
+                         .to(Xd.device))
+    return gs.spgemm(gs.DeviceCSR.from_scipy(Hc, Xd.device), Xd)
+
+
+class BatchSegments:
+    """The column grouping of a run of consecutive batches (gcg_minibatch_segment): batch b of
+    the run owns segments batch_seg_ptr[b] .. batch_seg_ptr[b+1]; segment s has column
+    seg_col[s] and entries seg_ptr[s] .. seg_ptr[s+1] of (ent_pos, ent_val)."""
+
+    def __init__(self, X: gs.DeviceCSR, perm: torch.Tensor, batch: int, nnz_sel: int):
+        gs._require_cuda(perm, "perm")
+        if perm.dtype != torch.int32 or perm.dim() != 1 or not perm.is_contiguous():
+            raise TypeError("perm must be a contiguous 1-D int32 tensor")
+        n_sel = perm.numel()
+        dev = X.device
+        cap, nb = C.c_int64(), C.c_size_t()
+        with torch.cuda.device(dev):
+            call("gcg_minibatch_segment_sizes", n_sel, batch, X.n_cols, nnz_sel, C.byref(cap),
+                 C.byref(nb))
+            self.n_batches = n_sel // batch
+            self.batch = batch
+            self.nnz_sel = nnz_sel
+            self.batch_seg_ptr = torch.empty(self.n_batches + 1, dtype=torch.int32, device=dev)
+            self.seg_col = torch.empty(cap.value, dtype=torch.int32, device=dev)
+            self.seg_ptr = torch.empty(cap.value + 1, dtype=torch.int32, device=dev)
+            self.ent_pos = torch.empty(max(nnz_sel, 1), dtype=torch.int32, device=dev)
+            self.ent_val = torch.empty(max(nnz_sel, 1), dtype=torch.float32, device=dev)
+            ws = torch.empty((nb.value + 7) // 8, dtype=torch.int64, device=dev)
+            call("gcg_minibatch_segment", X.n_rows, X.n_cols, _ptr(X.indptr), _ptr(X.indices),
+                 _ptr(X.data), _ptr(perm), n_sel, batch, nnz_sel, _ptr(self.batch_seg_ptr),
+                 _ptr(self.seg_col), _ptr(self.seg_ptr), _ptr(self.ent_pos), _ptr(self.ent_val),
+                 _ptr(ws), ws.numel() * 8, _stream_handle(dev))
+
+
+def w1_step(W: torch.Tensor, m: torch.Tensor, v: torch.Tensor, G: torch.Tensor,
+            seg: BatchSegments, b: int, l1: float, l2: float, a_t: torch.Tensor,
+            beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8) -> None:
+    """The W1 update of batch b of `seg` in one pass over W, m, v (gcg_minibatch_w1_step_f32):
+    g = (X[batch])^T . G + l1 sgn(W) + 2 l2 W, then Lasagne Adam with the step size a_t (device
+    scalar). G: [batch, K] float32 with unit column stride."""
+    for t, name in ((W, "W"), (m, "m"), (v, "v")):
+        gs._require_cuda(t, name)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != W.shape:
+            raise TypeError("w1_step needs contiguous float32 W, m, v of one shape")
+    F, K = W.shape
+    if G.dtype != torch.float32 or G.shape != (seg.batch, K) or (K > 1 and G.stride(1) != 1):
+        raise ValueError(f"G must be float32 [{seg.batch}, {K}] with unit column stride")
+    if not 0 <= b < seg.n_batches:
+        raise IndexError("batch index out of range")
+    ldg = G.stride(0) if seg.batch > 1 else max(K, 1)
+    with torch.cuda.device(W.device):
+        call("gcg_minibatch_w1_step_f32", F, K, _ptr(W), _ptr(m), _ptr(v), _ptr(G), ldg,
+             seg.batch, C.c_void_p(seg.batch_seg_ptr.data_ptr() + 4 * b), _ptr(seg.seg_col),
+             _ptr(seg.seg_ptr), _ptr(seg.ent_pos), _ptr(seg.ent_val), float(l1), float(l2),
+             _ptr(a_t), float(beta1), float(beta2), float(eps), _stream_handle(W.device))
+    increment_version(W)
+    increment_version(m)
+    increment_version(v)
+
+
+class MLP:
+    def __init__(self, n_epochs=10, batch_size=1000, init_parameters=None, complete_prob=False,
+                 add_hidden=True, regul_coefs=(5e-5, 5e-5), save_results=False,
+                 hidden_layer_size=None, drop_out=False, drop_out_coefs=(0.5, 0.5),
+                 early_stopping_max_down=100000, loss_name="log", nonlinearity="rectify",
+                 device="cuda"):
+        if complete_prob:
+            raise NotImplementedError("complete_prob (soft labels) is not built")
+        if drop_out:
+            raise NotImplementedError("drop_out is not built for the mini-batch MLP")
+        if loss_name != "log":
+            raise NotImplementedError("only the 'log' (categorical cross-entropy) loss is built")
+        self.n_epochs = n_epochs
+        self.batch_size = int(batch_size)
+        self.init_parameters = init_parameters
+        self.complete_prob = False
+        self.add_hidden = bool(add_hidden)
+        self.regul_coefs = list(regul_coefs)
+        self.save_results = save_results
+        self.hidden_layer_size = hidden_layer_size
+        self.drop_out = False
+        self.drop_out_coefs = list(drop_out_coefs)
+        self.early_stopping_max_down = early_stopping_max_down
+        self.loss_name = loss_name
+        self.nonlinearity = "rectify"  # the reference forces rectify (mlp.py:123)
+        self.device = torch.device(device)
+        self.history = []
+        # measurement hook (tools/bench_mlp.py): f(self, batch index, G, l1, l2) replaces the
+        # fused W1 step
+        self._w1_update = None
+        self._inputs = {}
+
+    # -- model --------------------------------------------------------------------------
+    def _build(self, in_size: int, out_size: int):
+        K = self.hidden_layer_size if self.add_hidden else out_size
+        init = self.init_parameters
+        if init is not None and len(init) != (4 if self.add_hidden else 2):
+            raise ValueError("init_parameters must be [W1, b1, W2, b2] (or [W, b] without a "
+                             "hidden layer), as lasagne.layers.get_all_param_values gives them")
+        dev = self.device
+
+        def param(x, shape):
+            return torch.nn.Parameter(_as_tensor(x, shape, dev), requires_grad=False)
+
+        # Lasagne GlorotUniform draws W1 then W2 from numpy's global stream, b = Constant(0.)
+        W1 = _glorot_uniform(in_size, K) if init is None else init[0]
+        self.W1 = param(W1, (in_size, K))
+        self.b1 = param(np.zeros(K, np.float32) if init is None else init[1], (K,))
+        self.params = [self.W1, self.b1]
+        if self.add_hidden:
+            W2 = _glorot_uniform(K, out_size) if init is None else init[2]
+            self.W2 = param(W2, (K, out_size)).requires_grad_(True)
+            self.b2 = param(np.zeros(out_size, np.float32) if init is None else init[3],
+                            (out_size,)).requires_grad_(True)
+            self.params += [self.W2, self.b2]
+        self.in_size, self.out_size, self.width = in_size, out_size, K
+        self._proj = dense.Projection()
+        # Adam state: W1's lives beside it (updated inside the W1 step kernel); b1 (, W2, b2) go
+        # through gcg_adam_step_f32 with the same device step size
+        self.optimizer = LasagneAdam(self.params[1:], lr=0.002, beta1=0.9, beta2=0.999,
+                                     epsilon=1e-8)
+        self.m1 = torch.zeros_like(self.W1)
+        self.v1 = torch.zeros_like(self.W1)
+
+    def _penalty_coefs(self):
+        """(l1, l2) of W1 and of W2: 0.5 shares of the layer's regul_coef (mlp.py:216-224);
+        without a hidden layer the one weight is the output layer's."""
+        c_out, c_hid = self.regul_coefs
+        c1 = c_hid if self.add_hidden else c_out
+        return (c1 * 0.5, c1 * 0.5), (c_out * 0.5, c_out * 0.5)
+
+    def _penalty(self) -> torch.Tensor:
+        p1, p2 = self._penalty_coefs()
+        if self.add_hidden:  # output layer first, as the reference adds them
+            return dense.l1l2_penalty([self.W2, self.W1], [p2, p1])
+        return dense.l1l2_penalty([self.W1], [p1])
+
+    def _input(self, X) -> gs.DeviceCSR:
+        if isinstance(X, gs.DeviceCSR):
+            Xd = X
+        elif sps.issparse(X):
+            Xd = _upload_cached(self._inputs, X.tocsr() if X.format != "csr" else X, self.device)
+        else:
+            raise ValueError("Input for this layer must be sparse")
+        if hasattr(self, "in_size") and Xd.n_cols != self.in_size:
+            raise ValueError(f"X has {Xd.n_cols} columns, the model {self.in_size}")
+        return Xd
+
+    def _first_layer(self, Xd: gs.DeviceCSR) -> torch.Tensor:
+        """rectify(X.W1 + b1) (the hidden layer's deterministic output), or the logits
+        X.W + b without a hidden layer -- sparse.spmm, as SparseInputDenseLayer runs it."""
+        return gs.spmm(Xd, self.W1.detach(), bias=self.b1.detach(),
+                       act="relu" if self.add_hidden else None)
+
+    def _output_loss(self, h: torch.Tensor, y: torch.Tensor):
+        """(mean CE, accuracy) of the output layer on the first layer's output."""
+        if not self.add_hidden:
+            return dense.softmax_xent(h, y)
+        if self.out_size <= dense.FUSED_MAX_COLS:
+            return self._proj.softmax_xent(h, self.W2, self.b2, y)
+        return dense.softmax_xent(self._proj.matmul(h, self.W2, self.b2), y)
+
+    @torch.no_grad()
+    def _evaluate(self, Xd: gs.DeviceCSR, y: torch.Tensor):
+        """f_val (mlp.py:247): deterministic loss with the penalty, and accuracy."""
+        loss, acc = self._output_loss(self._first_layer(Xd), y)
+        return loss + self._penalty(), acc
+
+    @torch.no_grad()
+    def _probabilities(self, Xd: gs.DeviceCSR) -> torch.Tensor:
+        h = self._first_layer(Xd)
+        if not self.add_hidden:
+            return dense.softmax(h)
+        if self.out_size <= dense.FUSED_MAX_COLS:
+            return self._proj.probabilities(h, self.W2, self.b2)
+        return dense.softmax(self._proj.matmul(h, self.W2, self.b2))
+
+    # -- training -----------------------------------------------------------------------
+    def _labels(self, Y, name: str) -> np.ndarray:
+        Y = np.asarray(Y)
+        if Y.ndim != 1 or not np.issubdtype(Y.dtype, np.integer):
+            raise ValueError(f"{name} must be a 1-D integer label array")
+        if Y.size and (int(Y.min()) < 0 or int(Y.max()) >= self.out_size):
+            raise ValueError(f"{name} holds a label outside [0, {self.out_size}): out_size is "
+                             "the number of distinct training labels (mlp.py:132)")
+        return Y.astype(np.int32)
+
+    def _prepare_epoch(self, order) -> None:
+        """Host half of an epoch: the order cut into whole batches, checked once, uploaded;
+        its labels gathered once; the runs of batches each segmentation call takes."""
+        B, n = self.batch_size, self.Xd.n_rows
+        order = np.asarray(order)
+        if order.ndim != 1 or order.size != n:
+            raise ValueError(f"an epoch's order must list the {n} training rows")
+        nb = n_batches(n, B)
+        perm = np.ascontiguousarray(order[:nb * B], dtype=np.int64)
+        if perm.min() < 0 or perm.max() >= n:
+            raise IndexError("epoch order out of range")
+        lens = self._indptr_host[perm + 1] - self._indptr_host[perm]
+        per_batch = lens.reshape(nb, B).sum(axis=1)
+        runs, start, acc = [], 0, 0
+        for b in range(nb):  # greedy runs of whole batches under SEGMENT_CHUNK_ENTRIES
+            if b > start and acc + int(per_batch[b]) > SEGMENT_CHUNK_ENTRIES:
+                runs.append((start, b, acc))
+                start, acc = b, 0
+            acc += int(per_batch[b])
+        runs.append((start, nb, acc))
+        self._runs = runs
+        self._perm_host = perm
+        self._perm = torch.from_numpy(perm.astype(np.int32)).to(self.device)
+        self._y_epoch = self._y_train.index_select(0, self._perm.to(torch.int64))
+        self._n_batches = nb
+
+    @torch.no_grad()
+    def _run_batches(self):
+        """Device half of an epoch: every batch's step, no host synchronisation. Returns the
+        last batch's (train loss with the penalty, accuracy) as device scalars."""
+        B, K, dev = self.batch_size, self.width, self.device
+        X, opt = self.Xd, self.optimizer
+        (l1, l2), pen2 = self._penalty_coefs()
+        act = GCG_ACT_RELU if self.add_hidden else GCG_ACT_NONE
+        loss = acc = None
+        for first, stop, nnz_sel in self._runs:
+            seg = BatchSegments(X, self._perm[first * B:stop * B], B, nnz_sel)
+            for b in range(first, stop):
+                rows = self._perm[b * B:(b + 1) * B]
+                y = self._y_epoch[b * B:(b + 1) * B]
+                last = b == self._n_batches - 1
+                h = gs.empty_dense(B, K, dev)
+                gate = gs.empty_gate(B, K, dev) if self.add_hidden else None
+                with torch.cuda.device(dev):
+                    # plan-less, one wave per batch row; the order was range-checked on the host
+                    call("gcg_spmm_csr_f32_gate", X.n_rows, X.n_cols, X.nnz, _ptr(X.indptr),
+                         _ptr(X.indices), _ptr(X.data), _ptr(self.W1), K, K, _ptr(h),
+                         h.stride(0) if B > 1 else max(K, 1), _ptr(self.b1), act, _ptr(rows), B,
+                         _ptr(gate), gate.stride(0) if gate is not None and B > 1 else
+                         (K + 3) // 4 * 4, _stream_handle(dev))
+                opt.zero_grad()
+                h.requires_grad_(True)
+                with torch.enable_grad():
+                    ce, a = self._output_loss(h, y)
+                    obj = ce
+                    if self.add_hidden:  # W2's penalty gradient; W1's is in the step kernel
+                        obj = ce + dense.l1l2_penalty([self.W2], [pen2])
+                obj.backward()
+                if last:  # the loss the reference reports: the last batch's, with the penalty
+                    loss, acc = ce.detach() + self._penalty(), a
+                g = h.grad if h.grad.stride(-1) == 1 else h.grad.contiguous()
+                if self.add_hidden:
+                    if K <= 1024:
+                        g, db1 = gs.relu_backward(g, gate=gate)
+                    else:  # the one-pass kernel's column limit, as layers._CSRMatMul
+                        g = g * (gate.to(g.dtype) * 0.5)
+                        db1 = g.sum(dim=0)
+                else:
+                    db1 = dense._colsum(g)
+                opt.prepare()
+                if self._w1_update is not None:
+                    self._w1_update(self, b, g, l1, l2)
+                else:
+                    w1_step(self.W1, self.m1, self.v1, g, seg, b - first, l1, l2, opt.a_t,
+                            opt.beta1, opt.beta2, opt.eps)
+                self.b1.grad = db1
+                opt.apply()
+        return loss, acc
+
+    def _train_epoch(self, order=None):
+        if order is None:
+            order = np.arange(self.Xd.n_rows)
+            np.random.shuffle(order)  # mlp.py:84-85, numpy's global stream
+        self._prepare_epoch(order)
+        return self._run_batches()
+
+    @torch.no_grad()
+    def fit(self, X_train, Y_train, X_dev, Y_dev, epoch_orders=None):
+        """mlp.py:125-289. epoch_orders (tests, measurement): one order of the training rows per
+        epoch instead of the np.random.shuffle draws."""
+        for X in (X_train, X_dev):
+            if not (isinstance(X, gs.DeviceCSR) or sps.issparse(X)):
+                raise ValueError("Input for this layer must be sparse")
+        in_size = X_train.shape[1]
+        self.out_size = output_size(Y_train)
+        log.info("output size is %d", self.out_size)
+        if not self.hidden_layer_size:
+            self.hidden_layer_size = default_hidden_size(self.out_size, in_size)
+        if self.add_hidden and self.hidden_layer_size < 1:
+            raise ValueError("hidden_layer_size must be at least 1")
+        y_train, y_dev = self._labels(Y_train, "Y_train"), self._labels(Y_dev, "Y_dev")
+        if X_train.shape[0] != y_train.size or X_dev.shape[0] != y_dev.size:
+            raise ValueError("X and Y must have the same number of rows")
+        n_batches(X_train.shape[0], self.batch_size)  # n < B raises
+        if X_dev.shape[1] != in_size:
+            raise ValueError("X_train and X_dev differ in width")
+        self.Xd = X_train if isinstance(X_train, gs.DeviceCSR) else \
+            gs.DeviceCSR.from_scipy(X_train, self.device)
+        self.Xdev = X_dev if isinstance(X_dev, gs.DeviceCSR) else \
+            gs.DeviceCSR.from_scipy(X_dev, self.device)
+        # the host copy of indptr: the sizes of every segmentation call (copied once)
+        self._indptr_host = (np.asarray(X_train.indptr) if sps.issparse(X_train) and
+                             X_train.format == "csr" else self.Xd.indptr.cpu().numpy()
+                             ).astype(np.int64)
+        self._build(in_size, self.out_size)
+        self._y_train = torch.from_numpy(y_train).to(self.device)
+        y_dev_d = torch.from_numpy(y_dev).to(self.device)
+        log.info("training (n_epochs, batch_size) = (%d, %d)", self.n_epochs, self.batch_size)
+        self.history = []
+        best_params, best_val_loss, best_val_acc, n_down = None, float("inf"), 0.0, 0
+        for n in range(self.n_epochs):
+            order = None if epoch_orders is None else epoch_orders[n]
+            l_train, acc_train = self._train_epoch(order)
+            l_val, acc_val = self._evaluate(self.Xdev, y_dev_d)
+            l_train, acc_train, l_val, acc_val = (float(x) for x in
+                                                  (l_train, acc_train, l_val, acc_val))
+            if acc_val > best_val_acc:
+                best_val_loss, best_val_acc, n_down = l_val, acc_val, 0
+                best_params = [p.detach().clone() for p in self.params]
+            else:
+                n_down += 1
+            self.history.append({"epoch": n, "train_loss": l_train, "train_acc": acc_train,
+                                 "val_loss": l_val, "val_acc": acc_val})
+            log.info("epoch %d ,train_loss %s ,acc %s ,val_loss %s ,acc %s,best_val_acc %s", n,
+                     l_train, acc_train, l_val, acc_val, best_val_acc)
+            if n_down > self.early_stopping_max_down:
+                log.info("validation results went down. early stopping ...")
+                break
+        if best_params is not None:
+            for p, b in zip(self.params, best_params):
+                p.copy_(b)
+        self.best_val_loss = best_val_loss
+        l_val, acc_val = self._evaluate(self.Xdev, y_dev_d)
+        self.best_dev_loss, self.best_dev_acc = float(l_val), float(acc_val)
+        log.info("Best dev acc: %f", self.best_dev_acc)
+        return self
+
+    # -- reference API ------------------------------------------------------------------
+    def predict_proba(self, X_test):
+        return self._probabilities(self._input(X_test)).cpu().numpy()
+
+    def predict(self, X_test):
+        return self._probabilities(self._input(X_test)).argmax(dim=1).cpu().numpy()
+
+    def accuracy(self, X_test, Y_test):
+        Xd = self._input(X_test)
+        y = torch.from_numpy(self._labels(Y_test, "Y_test")).to(self.device)
+        if y.numel() != Xd.n_rows:
+            raise ValueError("X and Y must have the same number of rows")
+        _loss, acc = self._evaluate(Xd, y)
+        return float(acc)
+
+    def score(self, X_test, Y_test):
+        return self.accuracy(X_test, Y_test)
+
+    @torch.no_grad()
+    def get_embedding(self, X):
+        """The hidden layer's deterministic output (mlp.py:201-202, 310-311)."""
+        if not self.add_hidden:
+            raise ValueError("get_embedding needs add_hidden=True (mlp.py:200-202)")
+        return self._first_layer(self._input(X)).cpu().numpy()
+
+    def get_params(self):
+        return [p.detach().cpu().numpy() for p in self.params]

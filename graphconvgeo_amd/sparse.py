@@ -423,6 +423,17 @@ class DeviceCSR:
             cache[rows.key] = t
         return t
 
+    def row_slice(self, start: int, stop: int) -> "DeviceCSR":
+        """Rows [start, stop) as a DeviceCSR without a host round trip of the entries: a rebased
+        indptr, views of indices / data (the X_conv[0:n_train] / dev / test slices of
+        tensormain.py:116-118). Python slice semantics for negative or out-of-range bounds."""
+        start, stop, _ = slice(start, stop).indices(self.n_rows)
+        stop = max(stop, start)
+        ptr = self.indptr[start:stop + 1]
+        lo, hi = (int(x) for x in ptr[[0, -1]].tolist())
+        return DeviceCSR(ptr - lo, self.indices[lo:hi], self.data[lo:hi],
+                         (stop - start, self.n_cols), validate=False)
+
     def gather_hint(self, row_bytes: int) -> Optional[torch.Tensor]:
         """Column indices with bit 31 set on the cold columns (gcg_spmm_csr_f32_planned_hint),
         or None where the hint does not pay (see GATHER_HINT_*). Built once per row size on the

@@ -315,6 +315,61 @@ gcg_status gcg_l1l2_grad_f32(int64_t n, const float* W, float l1, float l2,
                              const float* scale_dev, float* dW, gcg_stream_t stream);
 
 /*
+ * The mini-batch MLP trainer (reference mlp.py:96-311: a sparse-input MLP trained on shuffled
+ * mini-batches, mlp.py:77-92, 268-270; driven by tensormain.py:141-149 on X_conv = H * X).
+ *
+ * gcg_minibatch_segment: the column grouping of all the batches of an epoch (or of a run of its
+ * batches) at once. perm (device, n_sel = n_batches * batch row ids of X, the epoch's order
+ * with its tail dropped) cuts into n_batches consecutive batches. For batch b it produces the
+ * segments batch_seg_ptr[b] .. batch_seg_ptr[b + 1] of one global segment list: segment s has
+ * the column seg_col[s] (ascending inside a batch) and the entries seg_ptr[s] .. seg_ptr[s + 1];
+ * entry e is (ent_pos[e] = the row's position in its batch, in [0, batch); ent_val[e]). Inside
+ * a segment the entries keep batch order and, within one row, storage order -- the stable order
+ * of scipy's X[rows].T.tocsr() (duplicate entries stay separate, empty rows give none).
+ *   nnz_sel   the number of stored entries of the selected rows, known on the host (X's indptr
+ *             is there); it sizes the entry arrays and the launches. Slots past the rows' real
+ *             total end up outside every batch's range, entries past nnz_sel are dropped; a row
+ *             id outside [0, n_rows) counts as an empty row.
+ *   sizes     batch_seg_ptr int32[n_batches + 1], seg_col int32[seg_capacity], seg_ptr
+ *             int32[seg_capacity + 1], ent_pos int32[nnz_sel], ent_val float32[nnz_sel];
+ *             seg_capacity = min(nnz_sel, n_batches * n_cols) + 1 and the workspace size come
+ *             from gcg_minibatch_segment_sizes (either output may be NULL; seg_capacity is host
+ *             arithmetic, workspace_bytes asks hipcub and so needs a HIP device: rocPRIM sizes
+ *             its temporary per architecture). The number of segments stays on the device.
+ * The sort key is batch * n_cols + column in 32 bits: n_batches * n_cols >= 2^32 - 1 (or more
+ * than INT32_MAX entries) is GCG_ERR_INVALID_ARG. Asynchronous on `stream`: no allocation, no
+ * host synchronisation.
+ *
+ * gcg_minibatch_w1_step_f32: the whole update of the sparse-input weight W (F x K, contiguous)
+ * for one mini-batch in one pass over W, m, v -- no F x K gradient exists. For every element
+ *     d = sum over the entries e of row r's segment, in order, of ent_val[e] * G[ent_pos[e]][c]
+ *         (from +0.0, product and sum rounded separately; +0.0 for a row without a segment)
+ *     g = d + (l1 * sgn(w) + 2 * l2 * w)            the expression of gcg_l1l2_grad_f32, s = 1
+ *     m, v, w updated as gcg_adam_step_f32 does     a_t read from *step_dev
+ * -- bitwise the composition of (X[batch])^T . G scattered into zeros, gcg_l1l2_grad_f32 and
+ * gcg_adam_step_f32, and reproducible (no atomics). G: batch x K gradient of the layer's
+ * pre-activation (ldg >= K); seg_range: device int32[2], this batch's segment range
+ * (batch_seg_ptr + b); the other arrays as gcg_minibatch_segment wrote them. 16-B accesses when
+ * K % 4 == 0, ldg % 4 == 0 and W, m, v, G are 16-B aligned, dword accesses otherwise (any K).
+ */
+gcg_status gcg_minibatch_segment_sizes(int64_t n_sel, int64_t batch, int64_t n_cols,
+                                       int64_t nnz_sel, int64_t* seg_capacity,
+                                       size_t* workspace_bytes);
+gcg_status gcg_minibatch_segment(int64_t n_rows, int64_t n_cols, const int32_t* indptr,
+                                 const int32_t* indices, const float* vals, const int32_t* perm,
+                                 int64_t n_sel, int64_t batch, int64_t nnz_sel,
+                                 int32_t* batch_seg_ptr, int32_t* seg_col, int32_t* seg_ptr,
+                                 int32_t* ent_pos, float* ent_val, void* workspace,
+                                 size_t workspace_bytes, gcg_stream_t stream);
+gcg_status gcg_minibatch_w1_step_f32(int64_t F, int64_t K, float* W, float* m, float* v,
+                                     const float* G, int64_t ldg, int64_t batch,
+                                     const int32_t* seg_range, const int32_t* seg_col,
+                                     const int32_t* seg_ptr, const int32_t* ent_pos,
+                                     const float* ent_val, float l1, float l2,
+                                     const float* step_dev, float beta1, float beta2, float eps,
+                                     gcg_stream_t stream);
+
+/*
  * CSR transpose on the device (CSR(X^T) for the X^T . dZ1 gradient of
  * mlpconv.py:71). Output is sorted by (row, col) with stable order for equal
  * entries. out_indptr int32[n_cols+1], out_indices int32[nnz], out_vals f32[nnz].
