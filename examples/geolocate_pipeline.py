@@ -6,6 +6,8 @@ the graph work and the training on the GPU:
   GPU   gcg_project_mention_graph    celebrity filter + projection  (data.py:226-250,364-373)
   GPU   gcg_normalize_adjacency_f32  H = D^-1/2 (A+I) D^-1/2          (tensormain.py:168-181)
   GPU   MLPCONV.fit / accuracy / predict                              (tensormain.py:207-244)
+  GPU   --kdtree-bucket N: geo.assign_classes (k-d-tree region labels, data.py:399-421) and
+        MLPCONV.geo_eval (mean / median km, Acc@161, tensormain.py:38-54)
 
 Synthetic data: users live in one of `regions`; they mention other users mostly from their
 own region and use region-specific words, so the graph and the text both carry the label.
@@ -56,6 +58,9 @@ def main():
     ap.add_argument("--epochs", type=int, default=100)
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--celebrity", type=int, default=10)
+    ap.add_argument("--kdtree-bucket", type=int, default=0,
+                    help="N > 0: k-d-tree region labels with this bucket size (assignClasses) and "
+                         "the geolocation metrics; 0 keeps the stand-in latitude-band labels")
     args = ap.parse_args()
     import scipy.sparse as sps
     import torch
@@ -74,8 +79,17 @@ def main():
                           min_df=2, max_df=0.5, dtype=np.float32)
     X = sps.vstack([vec.fit_transform(df_train.text.values), vec.transform(df_dev.text.values),
                     vec.transform(df_test.text.values)]).tocsr().astype(np.float32)
-    lab = lambda df: (df["lat"].values - 40.0).astype(int)  # region labels (stand-in for kdtree)
-    Y = np.concatenate([lab(df_train), lab(df_dev), lab(df_test)])
+    medians = None
+    if args.kdtree_bucket > 0:  # DataLoader.assignClasses on the GPU
+        from graphconvgeo_amd.geo import assign_classes
+
+        locs = [df[["lat", "lon"]].values for df in (df_train, df_dev, df_test)]
+        *labels, medians = assign_classes(*locs, args.kdtree_bucket)
+        Y = torch.cat(labels).cpu().numpy()
+        regions = medians.shape[0]
+    else:
+        lab = lambda df: (df["lat"].values - 40.0).astype(int)  # stand-in region labels
+        Y = np.concatenate([lab(df_train), lab(df_dev), lab(df_test)])
     n_tr, n_dev = len(df_train), len(df_dev)
     train = np.random.default_rng(77).choice(n_tr, size=n_tr).astype(np.int32)  # tensormain.py:226
     dev = np.arange(n_tr, n_tr + n_dev, dtype=np.int32)
@@ -87,10 +101,15 @@ def main():
     torch.cuda.synchronize()
     t_fit = time.perf_counter() - t0
     acc = clf.accuracy("test", Y[test])
-    print(json.dumps({"users": len(Y), "graph_nnz": H.nnz, "features": X.shape[1],
-                      "graph_build_s": round(t_graph, 3), "fit_s": round(t_fit, 3),
-                      "epochs_run": len(clf.history), "test_acc": round(acc, 4),
-                      "chance": round(1.0 / regions, 4)}))
+    rec = {"users": len(Y), "graph_nnz": H.nnz, "features": X.shape[1],
+           "graph_build_s": round(t_graph, 3), "fit_s": round(t_fit, 3),
+           "epochs_run": len(clf.history), "test_acc": round(acc, 4),
+           "chance": round(1.0 / regions, 4)}
+    if medians is not None:
+        mean_km, median_km, acc161 = clf.geo_eval("test", locs[2], medians)
+        rec.update(classes=int(regions), mean_km=round(mean_km, 3), median_km=round(median_km, 3),
+                   acc_at_161=round(acc161, 3))
+    print(json.dumps(rec))
     return acc
 
 

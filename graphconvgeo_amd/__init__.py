@@ -11,6 +11,8 @@ Product modules (all compute runs in libgcg_spmm.so HIP kernels; no CPU fallback
   mentions     mention-graph parsing (host) and projection (HIP), data.py:226-375
   mlpconv      MLPCONV trainer (mlpconv.py:121-352) on the GPU
   mlp          MLP mini-batch trainer (mlp.py:96-311) on the GPU, input_convolution (H * X)
+  geo          k-d-tree region labels (kdtree.py), class medians, haversine, nearest class and
+               geo_eval (mean / median km, Acc@161) on the GPU, data.py:399-419
   synth        seeded synthetic graphs / features for the BASELINE configs
 
 `MLP`, `input_convolution` and `DeviceCSR` are imported lazily from the package itself.
@@ -28,7 +30,7 @@ __version__ = "0.1.0"
 _os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "8")
 
 __all__ = ["sparse", "ops", "layers", "dense", "distributed", "dist_train", "graph", "mentions",
-           "mlpconv", "mlp", "synth", "MLP", "input_convolution", "DeviceCSR"]
+           "mlpconv", "mlp", "geo", "synth", "MLP", "input_convolution", "DeviceCSR"]
 
 _LAZY = {"MLP": "mlp", "input_convolution": "mlp", "DeviceCSR": "sparse"}
 

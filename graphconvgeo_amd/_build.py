@@ -14,11 +14,11 @@ REPO_DIR = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
 # Translation units of libgcg_spmm.so: SpMM kernels + planner, CSR utilities, graph build,
 # SpGEMM, MFMA dense projection + softmax/xent, Philox dropout, the mini-batch MLP's epoch
-# segmentation and W1 step, error/version helpers. Compiled in parallel, linked into one shared
-# library.
+# segmentation and W1 step, k-d-tree labels + geolocation metrics, error/version helpers.
+# Compiled in parallel, linked into one shared library.
 SOURCES = [os.path.join(CSRC, f) for f in
            ("spmm.hip", "csr_ops.hip", "graph_build.hip", "spgemm.hip", "dense.hip", "dropout.hip",
-            "minibatch.hip", "errors.cpp")]
+            "minibatch.hip", "geo.hip", "errors.cpp")]
 INTERNAL_HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "index_kernels.h", "gemm_epilogue.inc",
                                                     "philox.h")]
 HEADER = os.path.join(REPO_DIR, "include", "gcg_spmm.h")

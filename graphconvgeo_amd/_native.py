@@ -122,6 +122,14 @@ SIGNATURES = {
                                   C.c_size_t, _p]),
     "gcg_spgemm": (C.c_int, [_i64, _i64, _i64, _i64, _p, _p, _p, C.c_int, _i64, _p, _p, _p,
                              C.c_int, _i64, _p, _p, _p, _p, _p]),
+    # geolocation labels and metrics (csrc/geo.hip)
+    "gcg_kdtree_fit_f64": (C.c_int, [_i64, _p, _i64, _p, _p, _p, _p, _pi64, _pi64, _pi64, _p, _p]),
+    "gcg_segment_medians_f64": (C.c_int, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
+    "gcg_class_medians_f64": (C.c_int, [_i64, _p, _p, _i64, _p, _p, _p]),
+    "gcg_haversine_km_f64": (C.c_int, [_i64, _p, _p, C.c_double, _p, _p]),
+    "gcg_nearest_class_f64": (C.c_int, [_i64, _p, _i64, _p, C.c_double, _p, _p, _p]),
+    "gcg_geo_eval_f64": (C.c_int, [_i64, _p, C.c_int, _p, _i64, _p, C.c_double, C.c_double, _p,
+                                   _p, _p, _p]),
     "gcg_spgemm_ex": (C.c_int, [_i64, _i64, _i64, _i64, _p, _p, _p, C.c_int, _i64, _p, _p, _p,
                                 C.c_int, _i64, _p, _p, _p, _p, C.c_int32, _i64, _p]),
 }

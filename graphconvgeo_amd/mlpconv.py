@@ -405,6 +405,19 @@ class MLPCONV:
         _loss, acc = self._loss_acc(rows, y)
         return float(acc)
 
+    @torch.no_grad()
+    def geo_eval(self, dataset_partition, locs, medians, earth_radius_km=None,
+                 threshold_km=161.0):
+        """(mean km, median km, acc_at_161) of tensormain.geo_eval (tensormain.py:38-54) for the
+        partition's predictions: the distance from each user's true location (`locs`, one
+        [lat, lon] row per row of the partition) to the median of the predicted class. The
+        predictions of predict() stay on the device (geo.geo_eval)."""
+        from . import geo
+
+        pred = self._probabilities(self._indices(dataset_partition)).argmax(dim=1)
+        radius = geo.EARTH_RADIUS_KM if earth_radius_km is None else earth_radius_km
+        return geo.geo_eval(pred, locs, medians, radius, threshold_km, device=self.device)
+
     def score(self, X, dataset_partition, y_true):
         """mlpconv.py:348-349 `score(X, dataset_partition, y_true)`. The reference forwards all
         three arguments to the two-argument accuracy() -- a TypeError there; this returns what

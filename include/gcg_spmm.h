@@ -20,6 +20,9 @@
  *   data.py:226-250,364-370 graph projection    gcg_project_mention_graph
  *   tensormain.py:170-180 H = D^-1/2 (A+I) D^-1/2  gcg_normalize_adjacency_f32
  *   main.py:530 / tensormain.py:114 X_conv = H * X gcg_spgemm_products + gcg_spgemm
+ *   data.py:399-419 assignClasses (kdtree.py)   gcg_kdtree_fit_f64, gcg_segment_medians_f64,
+ *                                               gcg_class_medians_f64, gcg_nearest_class_f64
+ *   tensormain.py:38-54 geo_eval                gcg_geo_eval_f64 (gcg_haversine_km_f64)
  *
  * Conventions (scipy CSR layout, as `scipy.sparse.csr_matrix` holds it):
  *   indptr  int32[n_rows + 1], indices int32[nnz], vals float32[nnz]; dense operands
@@ -656,6 +659,84 @@ gcg_status gcg_gemm_tn_f32(int64_t R, int64_t M, int64_t N, const float* A, int6
                            const float* B, int64_t ldb, const float* scale_dev /*nullable*/,
                            float* C, int64_t ldc, void* workspace, size_t workspace_bytes,
                            gcg_stream_t stream);
+
+/*
+ * Geolocation labels and metrics (csrc/geo.hip). Coordinates are row-major N x 2 float64
+ * [latitude, longitude] in degrees, 8-B aligned; all arithmetic is float64. Unlike the hot-path
+ * entries above, gcg_kdtree_fit_f64 and gcg_class_medians_f64 allocate their scratch with
+ * hipMallocAsync on `stream`, and gcg_kdtree_fit_f64 synchronizes the stream once per tree level.
+ *
+ * gcg_kdtree_fit_f64: the region labels of kdtree.KDTreeClustering(bucket_size).fit(locs)
+ * (kdtree.py:84-151), exactly: a node of more than bucket_size points splits on the axis of the
+ * larger max - min (a tie gives latitude) at np.median of that axis (split == max -> min; zero
+ * width -> leaf), `value > split` goes right, and leaves are numbered in pre-order, left first.
+ * Built level by level over two id lists kept sorted by latitude / longitude inside every node.
+ *   labels[N]      the leaf number of every point
+ *   perm_lat[N], perm_lon[N]  the point ids grouped by leaf, sorted by latitude / longitude
+ *                  inside each leaf
+ *   leaf_ptr[N+1]  capacity N + 1; leaf c is [leaf_ptr[c], leaf_ptr[c+1]) of both lists
+ *                  (entries 0 .. n_clusters are written)
+ *   n_clusters_host, depth_host (levels on which a node split; nullable), readbacks_host (the
+ *                  stream synchronizations made: depth + 2; nullable): HOST outputs
+ *   status_dev     device int32, set to 1 for a non-finite coordinate (the call then returns
+ *                  GCG_ERR_INVALID_ARG after the first level's readback; outputs undefined)
+ * N = 0 gives 0 clusters; bucket_size < 1 is GCG_ERR_INVALID_ARG. N <= 2^30 - 2.
+ */
+gcg_status gcg_kdtree_fit_f64(int64_t N, const double* locs, int64_t bucket_size,
+                              int32_t* labels, int32_t* perm_lat, int32_t* perm_lon,
+                              int32_t* leaf_ptr, int64_t* n_clusters_host,
+                              int64_t* depth_host /*nullable*/,
+                              int64_t* readbacks_host /*nullable*/, int32_t* status_dev,
+                              gcg_stream_t stream);
+
+/*
+ * medians[c] = (np.median of the latitudes, np.median of the longitudes) of segment
+ * [ptr[c], ptr[c+1]) of perm_lat / perm_lon (point ids sorted by that coordinate inside every
+ * segment, as gcg_kdtree_fit_f64 leaves them): a selection, or (a + b) / 2 of the two middle
+ * values, so bitwise numpy's. An empty or out-of-range segment gives NaN. medians: C x 2.
+ */
+gcg_status gcg_segment_medians_f64(int64_t C, int64_t N, const double* locs, const int32_t* ptr,
+                                   const int32_t* perm_lat, const int32_t* perm_lon,
+                                   double* medians, gcg_stream_t stream);
+
+/*
+ * Per-class medians of DataLoader.assignClasses (data.py:408-413) for any labels[N] in [0, C):
+ * a radix sort by coordinate, a stable one by class, then gcg_segment_medians_f64's lookup.
+ * A class without points gives NaN (np.median of nothing). *status_dev = 1 for a label outside
+ * [0, C) or a non-finite coordinate (medians are then undefined).
+ */
+gcg_status gcg_class_medians_f64(int64_t N, const double* locs, const int32_t* labels, int64_t C,
+                                 double* medians, int32_t* status_dev, gcg_stream_t stream);
+
+/*
+ * out[i] = great-circle distance in km between a[i] and b[i], as the `haversine` package the
+ * reference imports: 2 R asin(sqrt(sin^2(dlat/2) + cos(lat1) cos(lat2) sin^2(dlon/2))), with the
+ * square root's argument clamped to 1. The package's radius differs between its versions
+ * (6371 / 6371.0088), so it is an argument.
+ */
+gcg_status gcg_haversine_km_f64(int64_t M, const double* a, const double* b,
+                                double earth_radius_km, double* out, gcg_stream_t stream);
+
+/*
+ * The brute-force 1-nearest-neighbour of data.py:416-419: index[i] = argmin_c
+ * haversine(locs[i], medians[c]), the first index on ties; distance (nullable) = that minimum.
+ * One kernel, one query per thread, the medians staged through LDS in tiles of 2048. A NaN
+ * median is never the nearest. C >= 1 unless M = 0.
+ */
+gcg_status gcg_nearest_class_f64(int64_t M, const double* locs, int64_t C, const double* medians,
+                                 double earth_radius_km, int32_t* index,
+                                 double* distance /*nullable*/, gcg_stream_t stream);
+
+/*
+ * tensormain.geo_eval's per-user work (tensormain.py:38-50): distance[i] = haversine(locs[i],
+ * medians[pred[i]]) and *count_dev = the number of rows with distance < threshold_km (strict).
+ * pred: int32 (pred_is_int64 = 0) or int64 (1) device array. *status_dev = 1 when a prediction
+ * lies outside [0, C) (its distance is NaN and it is not counted). Both scalars are reset first.
+ */
+gcg_status gcg_geo_eval_f64(int64_t M, const void* pred, int pred_is_int64, const double* locs,
+                            int64_t C, const double* medians, double earth_radius_km,
+                            double threshold_km, double* distance, int64_t* count_dev,
+                            int32_t* status_dev, gcg_stream_t stream);
 
 #ifdef __cplusplus
 }
