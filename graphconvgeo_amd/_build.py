@@ -12,15 +12,16 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_DIR = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
-# Translation units of libgcg_spmm.so: SpMM kernels + planner, CSR utilities, graph build,
+# Translation units of libgcg_spmm.so: SpMM kernels + planner, the bf16-operand SpMM and its row
+# conversion, CSR utilities, graph build,
 # SpGEMM, MFMA dense projection + softmax/xent, Philox dropout, the mini-batch MLP's epoch
 # segmentation and W1 step, k-d-tree labels + geolocation metrics, error/version helpers.
 # Compiled in parallel, linked into one shared library.
 SOURCES = [os.path.join(CSRC, f) for f in
-           ("spmm.hip", "csr_ops.hip", "graph_build.hip", "spgemm.hip", "dense.hip", "dropout.hip",
+           ("spmm.hip", "spmm_bf16.hip", "csr_ops.hip", "graph_build.hip", "spgemm.hip", "dense.hip", "dropout.hip",
             "minibatch.hip", "geo.hip", "errors.cpp")]
-INTERNAL_HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "index_kernels.h", "gemm_epilogue.inc",
-                                                    "philox.h")]
+INTERNAL_HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "spmm_shared.h", "index_kernels.h",
+                                                    "gemm_epilogue.inc", "philox.h")]
 HEADER = os.path.join(REPO_DIR, "include", "gcg_spmm.h")
 LIB = os.path.join(PKG_DIR, "libgcg_spmm.so")
 ARCH = os.environ.get("GCG_OFFLOAD_ARCH", "gfx950")

@@ -50,6 +50,12 @@ SIGNATURES = {
                                                 C.c_int, _p, _i64, _p, C.c_size_t, _p, _p]),
     "gcg_relu_backward_gate_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p,
                                              C.c_size_t, _p]),
+    # bf16 dense operand (csrc/spmm_bf16.hip)
+    "gcg_rows_f32_to_bf16": (C.c_int, [_i64, _i64, _p, _i64, _p, _i64, _p]),
+    "gcg_spmm_csr_bf16z_f32": (C.c_int, [_i64, _i64, _i64, _p, _p, _p, _p, _i64, _i64, _p, _i64,
+                                         _p, C.c_int, _p, _i64, _p, _i64, _p]),
+    "gcg_spmm_csr_bf16z_f32_planned": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _i64, _p,
+                                                 C.c_int, _p, _i64, _p, C.c_size_t, _p, _p]),
     "gcg_dropout_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _i64, C.c_uint32, C.c_float,
                                   C.c_uint64, _p, C.c_uint32, _i64, _p, _p]),
     "gcg_dropout_relu_backward_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p,

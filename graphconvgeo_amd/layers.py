@@ -44,6 +44,18 @@ from . import sparse as gs
 
 _FUSED_ACTS = {"rectify": "relu", "relu": "relu"}
 
+# gather_dtype: the storage type of the dense operand an H-SpMM gathers. "bfloat16" (opt-in)
+# rounds the operand once (sparse.to_bf16_rows, round-to-nearest-even) and gathers half the
+# bytes; products and sums stay float32 (sparse.spmm with a bfloat16 Z). The backward rounds the
+# incoming gradient the same way and treats the forward's rounding as the identity.
+GATHER_DTYPES = ("float32", "bfloat16")
+
+
+def _check_gather_dtype(gather_dtype: str) -> str:
+    if gather_dtype not in GATHER_DTYPES:
+        raise ValueError(f"gather_dtype must be one of {GATHER_DTYPES}")
+    return gather_dtype
+
 
 def _glorot_uniform(fan_in: int, fan_out: int, rng=None) -> np.ndarray:
     """lasagne.init.GlorotUniform(gain=1.0).sample((num_inputs, num_units)), the default W of
@@ -116,7 +128,7 @@ class _CSRMatMul(torch.autograd.Function):
     positions; its backward regenerates the mask inside the rectify-backward pass."""
 
     @staticmethod
-    def forward(ctx, Z, bias, A: gs.DeviceCSR, act, rows, mode, drop=None):
+    def forward(ctx, Z, bias, A: gs.DeviceCSR, act, rows, mode, drop=None, bf16=False):
         gate = None
         if act == "relu" and any(ctx.needs_input_grad[:2]):
             # rectify gate (2/1/0 for pre-activation > 0, == 0, < 0) written by the SpMM
@@ -125,12 +137,14 @@ class _CSRMatMul(torch.autograd.Function):
             # alone cannot tell from a negative one
             n_out = A.n_rows if rows is None else len(rows)
             gate = gs.empty_gate(n_out, Z.shape[1], A.device)
-        Y = gs.spmm(A, Z, bias=bias, act=act, rows=rows, mode=mode, gate=gate)
+        Y = gs.spmm(A, gs.to_bf16_rows(Z) if bf16 else Z, bias=bias, act=act, rows=rows,
+                    mode=mode, gate=gate)
         if drop is not None:
             _drop.dropout_dense(Y, drop, out=Y)  # in place (gcg_dropout_f32)
         ctx.drop = drop
         ctx.A, ctx.act, ctx.rows, ctx.mode = A, act, rows, mode
         ctx.has_bias = bias is not None
+        ctx.bf16 = bf16
         ctx.save_for_backward(gate)
         return Y
 
@@ -156,7 +170,12 @@ class _CSRMatMul(torch.autograd.Function):
             g = gY * (gate.to(gY.dtype) * 0.5)
             g_bias = g.sum(dim=0) if want_bias else None
         g_Z = None
-        if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[0] and ctx.bf16:
+            # the gradient rounded once (after the rectify backward; the bias gradient above read
+            # the float32 one), then the bf16-gather SpMM with (A[rows])^T or A^T
+            T = A.rows_transpose(rows) if rows is not None else A.transpose()
+            g_Z = gs.spmm(T, gs.to_bf16_rows(g), mode=ctx.mode)
+        elif ctx.needs_input_grad[0]:
             if rows is not None:
                 # (A[rows])^T . g: one SpMM over the targets' nonzeros (sparse.rows_transpose),
                 # equal to A^T . inc_subtensor(zeros, rows, g) (mlpconv.py:94, Theano's grad)
@@ -167,7 +186,7 @@ class _CSRMatMul(torch.autograd.Function):
                               mode=ctx.mode)
             else:
                 g_Z = A.tmatmul(g if g.stride(-1) == 1 else g.contiguous(), mode=ctx.mode)
-        return g_Z, g_bias, None, None, None, None, None
+        return g_Z, g_bias, None, None, None, None, None, None
 
 
 def _index_csr_cached(rows: gs.RowSelection, n_rows: int):
@@ -179,12 +198,24 @@ def _index_csr_cached(rows: gs.RowSelection, n_rows: int):
 
 def csr_matmul(A: gs.DeviceCSR, Z: torch.Tensor, bias: Optional[torch.Tensor] = None,
                act: Optional[str] = None, rows: Optional[gs.RowSelection] = None,
-               mode: str = "auto", dropout: Optional["_drop.DropoutSpec"] = None) -> torch.Tensor:
+               mode: str = "auto", dropout: Optional["_drop.DropoutSpec"] = None,
+               gather_dtype: str = "float32") -> torch.Tensor:
     """Differentiable S.dot(A, Z) (+ bias, rectify, row subset) through the HIP kernels.
     Under torch.compile the registered op gcg::spmm_csr (graphconvgeo_amd.ops: same kernels,
     a fake kernel for tracing, its autograd formula made of gcg ops) stands in for the
     autograd.Function. dropout: a dropout.DropoutSpec masks the output (eager only, at most
-    1024 columns: the fused backward's limit)."""
+    1024 columns: the fused backward's limit). gather_dtype="bfloat16" (eager only): Z, and in
+    the backward the gradient, are rounded to bfloat16 once and gathered at half the bytes
+    (GATHER_DTYPES above); the mask, the bias gradient and the rectify backward stay float32."""
+    bf16 = _check_gather_dtype(gather_dtype) == "bfloat16"
+    if bf16:
+        if torch.compiler.is_compiling():
+            raise NotImplementedError(
+                "gather_dtype='bfloat16' is not available under torch.compile: the bf16-gather "
+                "kernels are not registered torch ops; run the layer eagerly")
+        if dropout is not None and Z.shape[1] > 1024:
+            raise NotImplementedError("output dropout takes at most 1024 columns")
+        return _CSRMatMul.apply(Z, bias, A, act, rows, mode, dropout, True)
     if dropout is not None:
         _drop._not_under_compile()
         if Z.shape[1] > 1024:
@@ -225,6 +256,9 @@ class GraphConvLayer(nn.Module):
     fused into the rectify backward (graphconvgeo_amd.dropout). The mask is keyed on the
     output's (row, column) positions. dropout_stream: a dropout.DropoutStream; None draws a
     seed after W, as Lasagne's DropoutLayer constructed after the DenseLayer does.
+
+    gather_dtype="bfloat16": the H-products (forward and backward) gather a bfloat16 copy of
+    their dense operand (csr_matmul); input . W stays float32.
     """
 
     def __init__(self, incoming=None, H=None, num_units: int = None, W=None, b=0.0,
@@ -232,8 +266,9 @@ class GraphConvLayer(nn.Module):
                  mode: str = "auto", require_sparse_input: bool = False, rng=None,
                  in_features: Optional[int] = None, dropout: float = 0.0,
                  dropout_stream: Optional["_drop.DropoutStream"] = None,
-                 dropout_rescale: bool = True):
+                 dropout_rescale: bool = True, gather_dtype: str = "float32"):
         super().__init__()
+        self.gather_dtype = _check_gather_dtype(gather_dtype)
         if num_units is None:
             raise ValueError("num_units is required")
         if H is None:
@@ -288,8 +323,10 @@ class GraphConvLayer(nn.Module):
             if self.post is not None:
                 raise NotImplementedError("output dropout needs a fused nonlinearity (rectify "
                                           "or linear): the mask is applied to the SpMM output")
-            return csr_matmul(self.H, Z, self.b, self.fused_act, rows, self.mode, dropout=drop)
-        Y = csr_matmul(self.H, Z, self.b, self.fused_act, rows, self.mode)
+            return csr_matmul(self.H, Z, self.b, self.fused_act, rows, self.mode, dropout=drop,
+                              gather_dtype=self.gather_dtype)
+        Y = csr_matmul(self.H, Z, self.b, self.fused_act, rows, self.mode,
+                       gather_dtype=self.gather_dtype)
         return self.post(Y) if self.post is not None else Y
 
     # Lasagne-style API
@@ -391,7 +428,8 @@ class ConvolutionDenseLayer(GraphConvLayer):
         if target_indices is not None:
             rows = target_indices if isinstance(target_indices, gs.RowSelection) else \
                 gs.RowSelection(target_indices, self.device)
-        return csr_matmul(self.H, input, None, None, rows, self.mode)
+        return csr_matmul(self.H, input, None, None, rows, self.mode,
+                          gather_dtype=self.gather_dtype)
 
     def forward(self, input, target_indices=None, deterministic: bool = False, **kwargs):
         sparse_in = isinstance(input, gs.DeviceCSR) or sps.issparse(input)
@@ -400,7 +438,10 @@ class ConvolutionDenseLayer(GraphConvLayer):
             # only GraphConvLayer.forward's generic path carries the mask
             raise NotImplementedError("output dropout on ConvolutionDenseLayer needs "
                                       "order='reference' and a fused nonlinearity")
+        # (the re-associated backward is float32 only: with a bfloat16 gather the reference order
+        # differentiates through dense.matmul + csr_matmul, Theano's association)
         if (self.order == "reference" and not sparse_in and REASSOCIATED_BACKWARD
+                and self.gather_dtype == "float32"
                 and self.fused_act is None and self.num_units > self.num_inputs
                 and torch.is_grad_enabled()):
             rows = None

@@ -39,7 +39,7 @@ from . import sparse as gs
 from ._native import call
 from .sparse import _ptr, _stream_handle
 from .dropout import DropoutStream, SparseInputDropoutLayer, draw_seed
-from .layers import ConvolutionDenseLayer, SparseConvolutionDenseLayer
+from .layers import GATHER_DTYPES, ConvolutionDenseLayer, SparseConvolutionDenseLayer
 
 log = logging.getLogger(__name__)
 
@@ -122,7 +122,7 @@ class MLPCONV:
                  early_stopping_max_down=100000, loss_name="log", nonlinearity="rectify",
                  dtype="float32", device="cuda", seed: Optional[int] = None, mode: str = "auto",
                  model_file: Optional[str] = None, report_k_epoch: int = 10,
-                 order: str = "auto", use_graph: bool = False):
+                 order: str = "auto", use_graph: bool = False, gather_dtype: str = "float32"):
         if dtype != "float32":
             raise ValueError("the GPU path computes in float32 (mlpconv.py dtype='float32')")
         self.drop_out = bool(drop_out)
@@ -156,6 +156,13 @@ class MLPCONV:
         if order not in ("reference", "propagate_first", "auto"):
             raise ValueError("order must be 'reference', 'propagate_first' or 'auto'")
         self.order = order
+        # "bfloat16": the four H-products of a step (two forward, two backward) gather a
+        # bfloat16 copy of their dense operand (layers.GATHER_DTYPES); X . W1 and X^T . dZ1 stay
+        # float32. Works with use_graph: the bfloat16 copies are temporaries of torch's
+        # allocator like the step's other intermediates, so the capture owns them.
+        if gather_dtype not in GATHER_DTYPES:
+            raise ValueError(f"gather_dtype must be one of {GATHER_DTYPES}")
+        self.gather_dtype = gather_dtype
         self.use_graph = use_graph  # replay each epoch's fwd+bwd+adam as one captured HIP graph
         # repeated targets (drawn with replacement) computed once, weighted by multiplicity
         self.distinct_targets = True
@@ -185,7 +192,8 @@ class MLPCONV:
                                                      stream_id=0)
         self.l_hid1 = SparseConvolutionDenseLayer(in_size, H=Hd, num_units=self.hidden_layer_size,
                                                   W=W1, nonlinearity="rectify", device=self.device,
-                                                  mode=self.mode, rng=rng, dropout=p_hid)
+                                                  mode=self.mode, rng=rng, dropout=p_hid,
+                                                  gather_dtype=self.gather_dtype)
         if self.drop_out and self.l_hid1.dropout_stream is None:  # p_hid == 0: still drawn
             self.l_hid1.dropout_stream = DropoutStream(draw_seed(rng), 1, self.device)
         self.dropout_streams = [] if not self.drop_out else \
@@ -193,6 +201,7 @@ class MLPCONV:
         self.l_out = ConvolutionDenseLayer(self.l_hid1, H=self.l_hid1.H, num_units=out_size,
                                            W=W2, nonlinearity=None, device=self.device,
                                            mode=self.mode, rng=rng,
+                                           gather_dtype=self.gather_dtype,
                                            order=trainer_order(self.order,
                                                                self.hidden_layer_size, out_size))
         if self.init_parameters is not None:

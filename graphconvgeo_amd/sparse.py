@@ -558,11 +558,11 @@ def _same_device(t: torch.Tensor, A: "DeviceCSR", name: str):
         raise ValueError(f"{name} is on {t.device} but the operator lives on {A.device}")
 
 
-def _check_dense(Z: torch.Tensor, A: DeviceCSR):
+def _check_dense(Z: torch.Tensor, A: DeviceCSR, bf16_ok: bool = False):
     _require_cuda(Z, "Z")
     _same_device(Z, A, "Z")
-    if Z.dtype != torch.float32:
-        raise TypeError(f"Z must be float32, got {Z.dtype}")
+    if Z.dtype != torch.float32 and not (bf16_ok and Z.dtype == torch.bfloat16):
+        raise TypeError(f"Z must be float32{' or bfloat16' if bf16_ok else ''}, got {Z.dtype}")
     if Z.dim() != 2 or Z.shape[0] != A.n_cols:
         raise ValueError(f"shape mismatch: A is {A.shape}, Z is {tuple(Z.shape)}")
     if Z.stride(1) != 1 and Z.shape[1] > 1:
@@ -641,6 +641,85 @@ def empty_gate(n: int, k: int, device) -> torch.Tensor:
     return buf[:, :k] if ld != k else buf
 
 
+def row_stride_bf16(k: int) -> int:
+    """Row stride (elements) of empty_dense_bf16's k-column rows: a multiple of 8 (16-B aligned
+    rows, one 16-B gather per lane whatever k is), chosen by row_stride's reasoning done in
+    bytes: the smallest such stride whose row starts keep a gathered row (2 k bytes) on the
+    fewest 128-B lines, else the next multiple of 128 B. Strides step by 16 B here, so a row
+    start can sit 0, 16, ... B into a line and only rows with that much slack in their last line
+    qualify for an unaligned stride. k = 300 (600 B, at least 5 lines, 40 B of slack): 304
+    elements (608 B) starts rows every 32 B into a line and part of them span 6 lines; no
+    stride below 320 keeps all rows on 5, so the rule gives 320 (640 B, every row exactly 5
+    lines, all on one alignment -- the shape that measured slower for f32 at 1280 B).
+    Measured at K = 300, 320 against 304 elements, interleaved on one box
+    (tools/bench_bf16_gather.py, profiles/bf16_gather/ab_layout.jsonl, ab_stride_us.jsonl):
+    World power-law 3.764 vs 3.885 ms, uniform 4.081 vs 4.201, Twitter-US 0.933 vs 0.961 and
+    0.966 vs 1.048 -- the one-alignment penalty of f32's 1280-B rows does not show at 640 B.
+    Padding is at most 63 elements."""
+    k8 = (k + 7) // 8 * 8
+    b = 2 * k
+    if k < 64 or b % 128 == 0:
+        return k8
+    slack = 128 * (-(-b // 128)) - b  # bytes a row may start into its first line
+    for ld in range(k8, k8 + 64, 8):
+        step = (2 * ld) % 128
+        if step and 128 - math.gcd(step, 128) <= slack:  # row starts: multiples of gcd
+            return ld
+    return (k + 63) // 64 * 64  # 128-B aligned rows: every row on the minimal line count
+
+
+def empty_dense_bf16(n: int, k: int, device) -> torch.Tensor:
+    """[n, k] bfloat16 view of an [n, row_stride_bf16(k)] buffer: the dense operand of the
+    bf16-gather SpMM (16-B aligned rows; to_bf16_rows zeroes the padding columns)."""
+    ld = row_stride_bf16(k) if k > 0 else 0
+    buf = torch.empty((n, ld), dtype=torch.bfloat16, device=device)
+    return buf[:, :k] if ld != k else buf
+
+
+def to_bf16_rows(Z: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Z (float32 [n, k]) rounded to bfloat16 rows, round-to-nearest-even, on the GPU
+    (gcg_rows_f32_to_bf16): the one place the bf16-gather mode approximates. out: a bfloat16
+    [n, k] tensor whose rows own their whole stride (empty_dense_bf16, the default): the columns
+    [k, stride) of every row, the last included, are written as zero. An `out` whose rows do not
+    start on a stride boundary of its storage (a column slice from column c > 0) or whose last
+    row's stride runs past the storage is refused: the zeros would land in its neighbours."""
+    _require_cuda(Z, "Z")
+    if Z.dtype != torch.float32 or Z.dim() != 2:
+        raise TypeError("to_bf16_rows converts a 2-D float32 tensor")
+    n, k = Z.shape
+    if (k > 1 and Z.stride(1) != 1) or (n > 1 and Z.stride(0) < k):  # transposed / expanded
+        Z = Z.contiguous()
+    if out is None:
+        out = empty_dense_bf16(n, k, Z.device)
+    else:
+        _require_cuda(out, "out")
+        if out.device != Z.device:
+            raise ValueError(f"out is on {out.device} but Z is on {Z.device}")
+        if out.dtype != torch.bfloat16 or out.shape != (n, k) or (k > 1 and out.stride(1) != 1):
+            raise ValueError(f"out must be bfloat16 [{n}, {k}] with unit column stride")
+    if n == 0 or k == 0:
+        return out
+    lds = Z.stride(0) if n > 1 else k
+    room = out.untyped_storage().nbytes() // out.element_size() - out.storage_offset()
+    if n > 1:
+        ldd = out.stride(0)
+        if ldd < k or out.storage_offset() % ldd or n * ldd > room:
+            raise ValueError("to_bf16_rows: out's rows must own their whole stride (start on a "
+                             "stride boundary of the storage, last row included)")
+    else:  # one row: its stride is the buffer's if that fits (empty_dense_bf16), else k
+        ldd = out.stride(0) if k <= out.stride(0) <= room else k
+    with torch.cuda.device(Z.device):
+        call("gcg_rows_f32_to_bf16", n, k, _ptr(Z), lds, _ptr(out), ldd, _stream_handle(Z.device))
+    return out
+
+
+def _gathers_bf16x8(Z, ldz: int, Y, ldy: int, bias) -> bool:
+    """Whether the bf16-operand launch gathers 16-B vectors (spmm_bf16.hip wide_ok)."""
+    if ldz % 8 or ldy % 4 or Z.data_ptr() % 16 or Y.data_ptr() % 16:
+        return False
+    return bias is None or bias.data_ptr() % 16 == 0
+
+
 def spmm(A: DeviceCSR, Z: torch.Tensor, bias: Optional[torch.Tensor] = None,
          act: Optional[str] = None, rows=None, mode: str = "auto",
          out: Optional[torch.Tensor] = None, task_nnz: int = 0,
@@ -656,6 +735,10 @@ def spmm(A: DeviceCSR, Z: torch.Tensor, bias: Optional[torch.Tensor] = None,
            A plain array/tensor runs plan-less (no plan to cache).
     gate : optional uint8 [n_out, K] (empty_gate) receiving the rectify gate 2/1/0 of every
            pre-activation (> 0, == 0, < 0) for Theano's rectify gradient (act='relu' only).
+    Z    : float32, or bfloat16 (to_bf16_rows) for the bf16-gather kernels: every element is
+           widened exactly, products and sums stay float32 in storage order, so the result is
+           the float32 one on Z.float() -- bitwise for 'ordered' / 'rowwise'. bias, out and
+           gate are float32 / float32 / uint8 either way.
     """
     if not isinstance(A, DeviceCSR):
         raise ValueError("Input for this layer must be sparse")
@@ -663,7 +746,8 @@ def spmm(A: DeviceCSR, Z: torch.Tensor, bias: Optional[torch.Tensor] = None,
         raise ValueError(f"mode must be one of {MODES}")
     if act not in ACTS:
         raise ValueError(f"unsupported activation {act!r}")
-    Z = _check_dense(Z, A)
+    Z = _check_dense(Z, A, bf16_ok=True)
+    bf16 = Z.dtype == torch.bfloat16
     K = Z.shape[1]
     sel = None
     rows_dev = None
@@ -716,7 +800,21 @@ def spmm(A: DeviceCSR, Z: torch.Tensor, bias: Optional[torch.Tensor] = None,
     if mode == "auto":
         mode = resolve_auto(A)
     with torch.cuda.device(A.device):
-        if mode == "rowwise":
+        if bf16 and mode == "rowwise":
+            call("gcg_spmm_csr_bf16z_f32", A.n_rows, A.n_cols, A.nnz, _ptr(A.indptr),
+                 _ptr(A.indices), _ptr(A.data), _ptr(Z), ldz, K, _ptr(out), ldy, _ptr(bias), actc,
+                 _ptr(rows_dev), n_out, _ptr(gate), ldg, stream)
+        elif bf16:
+            plan = A.plan(sel, ordered=ORDERED_PLAN if mode == "ordered" else 0,
+                          task_nnz=task_nnz)
+            ws = plan.workspace(K)
+            # the hot set sized for the bf16 row bytes; read by the 16-B launches only
+            hint = A.gather_hint(2 * min(ldz, 512)) if _gathers_bf16x8(Z, ldz, out, ldy, bias) \
+                else None
+            call("gcg_spmm_csr_bf16z_f32_planned", plan.handle, _ptr(A.indptr), _ptr(A.indices),
+                 _ptr(A.data), _ptr(Z), ldz, K, _ptr(out), ldy, _ptr(bias), actc, _ptr(gate), ldg,
+                 _ptr(ws), 0 if ws is None else ws.numel() * 4, _ptr(hint), stream)
+        elif mode == "rowwise":
             call("gcg_spmm_csr_f32_gate", A.n_rows, A.n_cols, A.nnz, _ptr(A.indptr),
                  _ptr(A.indices), _ptr(A.data), _ptr(Z), ldz, K, _ptr(out), ldy, _ptr(bias), actc,
                  _ptr(rows_dev), n_out, _ptr(gate), ldg, stream)

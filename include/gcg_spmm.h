@@ -176,6 +176,47 @@ gcg_status gcg_spmm_csr_f32_planned_hint(const gcg_spmm_plan* plan, const int32_
                                          gcg_stream_t stream);
 
 /*
+ * bf16 dense operand (opt-in). gcg_rows_f32_to_bf16 converts n rows of K floats (row stride lds)
+ * to bf16 rows (uint16_t storage, row stride ldd >= K) with round-to-nearest-even: NaN stays NaN
+ * (the quiet NaN 0x7FC0), +-Inf stays +-Inf, a finite value above the bf16 range rounds to Inf.
+ * Destination columns [K, ldd) are written as zero, so a masked last vector of the SpMM never
+ * reads garbage. 16-B loads and stores when lds % 4 == 0, ldd % 8 == 0 and both bases are 16-B
+ * aligned; any other layout converts element by element (src 4-B, dst 2-B aligned). One pass,
+ * allocates nothing.
+ *
+ * gcg_spmm_csr_bf16z_f32 / _planned: the contracts of gcg_spmm_csr_f32_gate and
+ * gcg_spmm_csr_f32_planned_hint with Z stored as bf16:
+ *       Y[i, 0:K] = act( sum_{j in row r, storage order} vals[j] * widen(Zb[indices[j], 0:K]) + bias )
+ * widen (bf16 -> f32) is exact, product and sum are f32, each rounded, in storage order: for
+ * Zr = widen(Zb) the result is bitwise scipy float32 `H @ Zr` (planned: ordered plans; fast plans
+ * within 1e-5 of it, bitwise on rows they do not split). vals, bias, Y, the gate bytes and the
+ * workspace stay as in the f32 calls (gcg_spmm_plan_workspace_bytes is valid as it is; plans
+ * depend on H only and serve both operand types). gate and gather_hint are nullable; the hint's
+ * hot set should be sized for the bf16 row bytes.
+ * Layout: 16-B gathers (8 bf16 per lane) when ldz % 8 == 0 and Zb is 16-B aligned, ldy % 4 == 0
+ * and Y / bias (/ workspace) are 16-B aligned; when K % 8 != 0 the last vector of a row also
+ * READS Zb's columns [K, round8(K)) -- inside the row since ldz % 8 == 0, never used. Any other
+ * layout (any ldz >= K, Zb 2-B aligned) takes the narrower fallback that gathers single elements:
+ * the same result, bitwise. GCG_ERR_INVALID_ARG for ldz < K or ldy < K, GCG_ERR_MISALIGNED for a
+ * Zb that is not 2-B or a Y / bias that is not 4-B aligned.
+ */
+gcg_status gcg_rows_f32_to_bf16(int64_t n, int64_t K, const float* src, int64_t lds,
+                                uint16_t* dst, int64_t ldd, gcg_stream_t stream);
+gcg_status gcg_spmm_csr_bf16z_f32(int64_t n_rows, int64_t n_cols, int64_t nnz,
+                                  const int32_t* indptr, const int32_t* indices,
+                                  const float* vals, const uint16_t* Zb, int64_t ldz, int64_t K,
+                                  float* Y, int64_t ldy, const float* bias, int act,
+                                  const int32_t* out_rows, int64_t n_out, uint8_t* gate,
+                                  int64_t ldgate, gcg_stream_t stream);
+gcg_status gcg_spmm_csr_bf16z_f32_planned(const gcg_spmm_plan* plan, const int32_t* indptr,
+                                          const int32_t* indices, const float* vals,
+                                          const uint16_t* Zb, int64_t ldz, int64_t K, float* Y,
+                                          int64_t ldy, const float* bias, int act, uint8_t* gate,
+                                          int64_t ldgate, void* workspace,
+                                          size_t workspace_bytes, const int32_t* gather_hint,
+                                          gcg_stream_t stream);
+
+/*
  * Host-only planner (no device memory, no HIP calls): the task list the plan uses,
  * exposed for testing and for host-side tools. `tasks_host` receives n_tasks int32
  * quadruples {a, b, c, d}: c == -4 -> column slice b of d of the row at position a (ordered);

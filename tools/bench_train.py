@@ -60,6 +60,8 @@ def main():
                          "(layers.REASSOCIATED_BACKWARD off)")
     ap.add_argument("--dropout", type=float, nargs=2, default=None, metavar=("P_HID", "P_IN"),
                     help="time the step with drop_out=True, dropout_coefs=[P_HID, P_IN]")
+    ap.add_argument("--gather-dtype", default="float32", choices=["float32", "bfloat16"],
+                    help="storage type of the dense operand the four H-products gather")
     args = ap.parse_args()
     gs.WIDE_ROW_ALIGN = not args.legacy_stride
     if args.theano_backward:
@@ -98,7 +100,7 @@ def main():
 
     clf = MLPCONV(n_epochs=0, hidden_layer_size=cfg.hidden, device=dev, seed=1, mode=args.mode,
                   order=args.order, use_graph=args.graph, drop_out=args.dropout is not None,
-                  dropout_coefs=args.dropout or (0.5, 0.5))
+                  dropout_coefs=args.dropout or (0.5, 0.5), gather_dtype=args.gather_dtype)
     clf.fit(X, train, dev_idx, test_idx, Y, H)  # builds layers, uploads H/X, no epochs
     y_train = torch.as_tensor(Y[train].astype(np.int32), device=dev)
     opt = LasagneAdam(clf.params)
@@ -134,7 +136,7 @@ def main():
     total = sp + sp_fwd_rows
     rec = {"metric": "GCN 2-layer fwd+bwd+adam step", "config": cfg.name, "ms_per_step": round(ms, 3),
            "median_ms_per_step": round(float(np.median(per_step)), 3) if per_step else None,
-           "dropout": args.dropout,
+           "dropout": args.dropout, "gather_dtype": args.gather_dtype,
            "nodes": n, "nnz_H": nnzH, "nnz_X": nnzX, "F": cfg.n_features, "K": K, "C": C,
            "train_rows": len(train), "train_rows_distinct": int(uniq.size),
            "spmm_algorithmic_bytes_per_step": total,
