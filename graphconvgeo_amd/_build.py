@@ -21,7 +21,8 @@ SOURCES = [os.path.join(CSRC, f) for f in
            ("spmm.hip", "spmm_bf16.hip", "csr_ops.hip", "graph_build.hip", "spgemm.hip", "dense.hip", "dropout.hip",
             "minibatch.hip", "geo.hip", "errors.cpp")]
 INTERNAL_HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "spmm_shared.h", "index_kernels.h",
-                                                    "gemm_epilogue.inc", "philox.h")]
+                                                    "gemm_epilogue.inc", "philox.h",
+                                                    "rectify_backward_pass.inc")]
 HEADER = os.path.join(REPO_DIR, "include", "gcg_spmm.h")
 LIB = os.path.join(PKG_DIR, "libgcg_spmm.so")
 ARCH = os.environ.get("GCG_OFFLOAD_ARCH", "gfx950")

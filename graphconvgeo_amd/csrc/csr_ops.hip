@@ -113,160 +113,37 @@ __device__ __forceinline__ float gate_apply(float g, uint32_t code) {
   return code == 2u ? g : (code == 1u ? 0.5f * g : 0.0f);
 }
 
+// Where the mask of the pass comes from: none (g = t), Y > 0, or the gate bytes.
+enum MaskSource { kMaskNone, kMaskY, kMaskGate };
+
+// Both kernels are the one pass of rectify_backward_pass.inc (see there for why it is included
+// and not called). MASK = false: column sums of gY only -- the bias gradient of a projection.
 template <int VEC, bool MASK, bool GATE = false>
 __global__ __launch_bounds__(256) void relu_backward_kernel(
     int64_t M, int K, int64_t rows_per_block, const float* gY, int64_t ldg,
     const float* __restrict__ Y, int64_t ldy, float* g_out, int64_t ldo,
     float* __restrict__ partial, const uint8_t* __restrict__ gate = nullptr,
     int64_t ldgate = 0) {
-  __shared__ float red[4][kReluMaxK4 * 64 * 4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t r0 = static_cast<int64_t>(blockIdx.x) * rows_per_block;
-  const int64_t r1 = min(M, r0 + rows_per_block);
-  const int pieces = (K + 64 * VEC - 1) / (64 * VEC);
-  float acc[kReluMaxK4][VEC];
-#pragma unroll
-  for (int p = 0; p < kReluMaxK4; ++p)
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) acc[p][e] = 0.f;
-#pragma unroll 2
-  for (int64_t r = r0 + w; r < r1; r += 4) {
-    const float* gr = gY + r * ldg;
-    const float* yr = (MASK && !GATE) ? Y + r * ldy : nullptr;
-    const uint8_t* gt = GATE ? gate + r * ldgate : nullptr;
-    float* orow = MASK ? g_out + r * ldo : nullptr;
-#pragma unroll
-    for (int p = 0; p < kReluMaxK4; ++p) {
-      if (p >= pieces) break;
-      const int c = (p * 64 + lane) * VEC;
-      if (c >= K) continue;
-      if constexpr (VEC == 4) {
-        if (c + 4 > K) {  // ragged tail: element-wise, never touches columns >= K
-          for (int e = 0; e < 4; ++e)
-            if (c + e < K) {
-              float o = gr[c + e];
-              if constexpr (GATE) {
-                o = gate_apply(o, gt[c + e]);
-                orow[c + e] = o;
-              } else if constexpr (MASK) {
-                o = yr[c + e] > 0.f ? o : 0.f;
-                orow[c + e] = o;
-              }
-              acc[p][e] += o;
-            }
-          continue;
-        }
-        float4 o = *reinterpret_cast<const float4*>(gr + c);
-        if constexpr (GATE) {
-          const uint32_t gv = *reinterpret_cast<const uint32_t*>(gt + c);
-          o = make_float4(gate_apply(o.x, gv & 0xffu), gate_apply(o.y, (gv >> 8) & 0xffu),
-                          gate_apply(o.z, (gv >> 16) & 0xffu), gate_apply(o.w, gv >> 24));
-          *reinterpret_cast<float4*>(orow + c) = o;
-        } else if constexpr (MASK) {
-          const float4 yv = *reinterpret_cast<const float4*>(yr + c);
-          o = make_float4(yv.x > 0.f ? o.x : 0.f, yv.y > 0.f ? o.y : 0.f,
-                          yv.z > 0.f ? o.z : 0.f, yv.w > 0.f ? o.w : 0.f);
-          *reinterpret_cast<float4*>(orow + c) = o;
-        }
-        acc[p][0] += o.x; acc[p][1] += o.y; acc[p][2] += o.z; acc[p][3] += o.w;
-      } else {
-        float o = gr[c];
-        if constexpr (GATE) {
-          o = gate_apply(o, gt[c]);
-          orow[c] = o;
-        } else if constexpr (MASK) {
-          o = yr[c] > 0.f ? o : 0.f;
-          orow[c] = o;
-        }
-        acc[p][0] += o;
-      }
-    }
-  }
-  // combine the 4 waves (fixed order), one partial row per block
-#pragma unroll
-  for (int p = 0; p < kReluMaxK4; ++p)
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) red[w][(p * 64 + lane) * VEC + e] = acc[p][e];
-  __syncthreads();
-  for (int c = threadIdx.x; c < K; c += 256) {
-    const float v = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
-    partial[static_cast<int64_t>(blockIdx.x) * K + c] = v;
-  }
+  constexpr MaskSource kMask = GATE ? kMaskGate : (MASK ? kMaskY : kMaskNone);
+  constexpr bool kDrop = false;
+  const DropKey d{};  // (unread without kDrop)
+  const int64_t row0 = 0;
+#include "rectify_backward_pass.inc"
 }
 
-// relu_backward_kernel<., true, GATE> behind a dropout mask (gcg_dropout_relu_backward_f32):
-// the gradient of drop(rectify(.)) in the same single pass. t = keep ? gY * scale : 0 from the
-// element's Philox word (row0 + r, column c: one call per dwordx4 piece), then the gate rule
-// (GATE = false: g = t). Row blocks, wave interleave, accumulation order and the partial
-// layout are relu_backward_kernel's, so the column sums are bitwise what that kernel gives on
-// the pre-masked gradient.
+// The gradient of drop(rectify(.)) (gcg_dropout_relu_backward_f32): the dropout mask, then the
+// gate rule (GATE = false: g = t), in the same single pass.
 template <int VEC, bool GATE>
 __global__ __launch_bounds__(256) void dropout_relu_backward_kernel(
     int64_t M, int K, int64_t rows_per_block, const float* gY, int64_t ldg, float* g_out,
     int64_t ldo, float* __restrict__ partial, const uint8_t* __restrict__ gate, int64_t ldgate,
     DropKey d, const int32_t* __restrict__ step_dev, int64_t row0) {
-  __shared__ float red[4][kReluMaxK4 * 64 * 4];
+  constexpr MaskSource kMask = GATE ? kMaskGate : kMaskNone;
+  constexpr bool kDrop = true;
+  const float* const Y = nullptr;  // (unread without kMaskY)
+  const int64_t ldy = 0;
   d.step = static_cast<uint32_t>(*step_dev);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t r0 = static_cast<int64_t>(blockIdx.x) * rows_per_block;
-  const int64_t r1 = min(M, r0 + rows_per_block);
-  const int pieces = (K + 64 * VEC - 1) / (64 * VEC);
-  float acc[kReluMaxK4][VEC];
-#pragma unroll
-  for (int p = 0; p < kReluMaxK4; ++p)
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) acc[p][e] = 0.f;
-#pragma unroll 2
-  for (int64_t r = r0 + w; r < r1; r += 4) {
-    const float* gr = gY + r * ldg;
-    const uint8_t* gt = GATE ? gate + r * ldgate : nullptr;
-    float* orow = g_out + r * ldo;
-    const int64_t i = row0 + r;
-#pragma unroll
-    for (int p = 0; p < kReluMaxK4; ++p) {
-      if (p >= pieces) break;
-      const int c = (p * 64 + lane) * VEC;
-      if (c >= K) continue;
-      if constexpr (VEC == 4) {
-        const Philox4 pw = drop_words(d, i, c >> 2);
-        if (c + 4 > K) {  // ragged tail: element-wise, never touches columns >= K
-          for (int e = 0; e < 4; ++e)
-            if (c + e < K) {
-              float o = drop_apply(d, pw.w[e], gr[c + e]);
-              if constexpr (GATE) o = gate_apply(o, gt[c + e]);
-              orow[c + e] = o;
-              acc[p][e] += o;
-            }
-          continue;
-        }
-        float4 o = *reinterpret_cast<const float4*>(gr + c);
-        o = make_float4(drop_apply(d, pw.w[0], o.x), drop_apply(d, pw.w[1], o.y),
-                        drop_apply(d, pw.w[2], o.z), drop_apply(d, pw.w[3], o.w));
-        if constexpr (GATE) {
-          const uint32_t gv = *reinterpret_cast<const uint32_t*>(gt + c);
-          o = make_float4(gate_apply(o.x, gv & 0xffu), gate_apply(o.y, (gv >> 8) & 0xffu),
-                          gate_apply(o.z, (gv >> 16) & 0xffu), gate_apply(o.w, gv >> 24));
-        }
-        *reinterpret_cast<float4*>(orow + c) = o;
-        acc[p][0] += o.x; acc[p][1] += o.y; acc[p][2] += o.z; acc[p][3] += o.w;
-      } else {
-        float o = drop_element(d, i, c, gr[c]);
-        if constexpr (GATE) o = gate_apply(o, gt[c]);
-        orow[c] = o;
-        acc[p][0] += o;
-      }
-    }
-  }
-  // combine the 4 waves (fixed order), one partial row per block
-#pragma unroll
-  for (int p = 0; p < kReluMaxK4; ++p)
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) red[w][(p * 64 + lane) * VEC + e] = acc[p][e];
-  __syncthreads();
-  for (int c = threadIdx.x; c < K; c += 256) {
-    const float v = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
-    partial[static_cast<int64_t>(blockIdx.x) * K + c] = v;
-  }
+#include "rectify_backward_pass.inc"
 }
 
 // out[c] = sum over the partial rows of partial[b][c], in a fixed order: workgroup = 16 waves
@@ -533,34 +410,47 @@ gcg_status gcg_relu_backward_f32_workspace_bytes(int64_t M, int64_t K, size_t* b
 
 namespace {
 
-// shared by gcg_relu_backward_f32 (MASK: Y), gcg_relu_backward_gate_f32 (MASK: gate bytes)
-// and gcg_column_sum_f32 (no mask)
-gcg_status relu_colsum(const char* fn, bool mask, int64_t M, int64_t K, const float* gY,
-                       int64_t ldg, const float* Y, int64_t ldy, float* g_out, int64_t ldo,
-                       float* bias_grad, void* workspace, size_t workspace_bytes,
-                       gcg_stream_t stream, const uint8_t* gate = nullptr, int64_t ldgate = 0) {
-  if (M < 0 || K < 0 || K > 64 * 4 * kReluMaxK4)
+// What the dropout entry adds to the pass: the stream's key (its step is read on the device)
+// and the logical row of row 0.
+struct DropArgs {
+  DropKey key;
+  const int32_t* step_dev;
+  int64_t row0;
+};
+
+// The host side of the pass for all four entries: gcg_relu_backward_f32 (kMaskY),
+// gcg_relu_backward_gate_f32 (kMaskGate), gcg_column_sum_f32 (kMaskNone, no g_out) and
+// gcg_dropout_relu_backward_f32 (drop; kMaskGate or kMaskNone, g_out always written).
+gcg_status rectify_backward(const char* fn, MaskSource mask, const DropArgs* drop, int64_t M,
+                            int64_t K, const float* gY, int64_t ldg, const float* Y, int64_t ldy,
+                            const uint8_t* gate, int64_t ldgate, float* g_out, int64_t ldo,
+                            float* bias_grad, void* workspace, size_t workspace_bytes,
+                            gcg_stream_t stream) {
+  if (M < 0 || K < 0 || K > 64 * 4 * kReluMaxK4 || (drop != nullptr && drop->row0 < 0))
     return fail(GCG_ERR_INVALID_ARG, "%s: bad sizes M=%lld K=%lld (K <= %d)", fn,
                 static_cast<long long>(M), static_cast<long long>(K), 64 * 4 * kReluMaxK4);
   auto st = static_cast<hipStream_t>(stream);
-  if (M == 0 || K == 0) {
+  if (M == 0 || K == 0) {  // an empty sum is zero
     if (bias_grad != nullptr && K > 0)
       GCG_HIP_CHECK(hipMemsetAsync(bias_grad, 0, sizeof(float) * K, st));
     return GCG_OK;
   }
-  const bool use_gate = mask && gate != nullptr;
-  if (use_gate) {  // the gate stands in for Y
-    if (ldgate < K || ldgate % 4 != 0 || !aligned(gate, 4))
-      return fail(GCG_ERR_MISALIGNED, "%s: gate needs ldgate >= K, ldgate %% 4 == 0, 4-B base", fn);
-    Y = gY;
-    ldy = ldg;
-  }
-  if (gY == nullptr || (mask && (Y == nullptr || g_out == nullptr)) ||
-      (!mask && bias_grad == nullptr))
+  const bool use_y = mask == kMaskY, store = mask != kMaskNone || drop != nullptr;
+  const bool bad_gate =
+      mask == kMaskGate && (ldgate < K || ldgate % 4 != 0 || !aligned(gate, 4));
+  // (the gate is looked at before the operands without dropout and after them with it: a call
+  // with both wrong keeps the status each entry has always given)
+  if (bad_gate && drop == nullptr)
+    return fail(GCG_ERR_MISALIGNED, "%s: gate needs ldgate >= K, ldgate %% 4 == 0, 4-B base", fn);
+  if (gY == nullptr || (store && g_out == nullptr) || (use_y && Y == nullptr) ||
+      (!store && bias_grad == nullptr) || (drop != nullptr && drop->step_dev == nullptr))
     return fail(GCG_ERR_INVALID_ARG, "%s: null operand", fn);
-  if (ldg < K || (mask && (ldy < K || ldo < K)))
+  if (ldg < K || (store && ldo < K) || (use_y && ldy < K))
     return fail(GCG_ERR_INVALID_ARG, "%s: ld < K", fn);
-  if (!aligned(gY, 4) || (mask && (!aligned(Y, 4) || !aligned(g_out, 4))))
+  if (bad_gate)
+    return fail(GCG_ERR_MISALIGNED, "%s: gate needs ldgate >= K, ldgate %% 4 == 0, 4-B base", fn);
+  if (!aligned(gY, 4) || (store && !aligned(g_out, 4)) || (use_y && !aligned(Y, 4)) ||
+      (drop != nullptr && !aligned(drop->step_dev, 4)))
     return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B aligned", fn);
   const int64_t rpb = relu_rows_per_block(M);
   const int64_t n_blocks = (M + rpb - 1) / rpb;
@@ -570,24 +460,31 @@ gcg_status relu_colsum(const char* fn, bool mask, int64_t M, int64_t K, const fl
   if (!aligned(workspace, 4)) return fail(GCG_ERR_MISALIGNED, "%s: workspace alignment", fn);
   float* part = static_cast<float*>(workspace);
   const bool vec = ldg % 4 == 0 && aligned(gY, 16) &&
-                   (!mask || (ldy % 4 == 0 && ldo % 4 == 0 && aligned(Y, 16) && aligned(g_out, 16)));
+                   (!store || (ldo % 4 == 0 && aligned(g_out, 16))) &&
+                   (!use_y || (ldy % 4 == 0 && aligned(Y, 16)));
   if (!vec && K > 64 * kReluMaxK4)
     return fail(GCG_ERR_MISALIGNED, "%s: K > %d needs 16-B rows (ld %% 4 == 0)", fn,
                 64 * kReluMaxK4);
   const dim3 grid(static_cast<unsigned>(n_blocks));
-#define GCG_RELU_LAUNCH(V, MK, GT)                                                              \
-  hipLaunchKernelGGL((relu_backward_kernel<V, MK, GT>), grid, dim3(256), 0, st, M, int(K), rpb,  \
-                     gY, ldg, Y, ldy, g_out, ldo, part, gate, ldgate)
+#define GCG_PASS_LAUNCH(V, MK)                                                                  \
+  if (drop != nullptr)                                                                          \
+    hipLaunchKernelGGL((dropout_relu_backward_kernel<V, MK == kMaskGate>), grid, dim3(256), 0,  \
+                       st, M, int(K), rpb, gY, ldg, g_out, ldo, part, gate, ldgate, drop->key,  \
+                       drop->step_dev, drop->row0);                                             \
+  else                                                                                          \
+    hipLaunchKernelGGL((relu_backward_kernel<V, MK != kMaskNone, MK == kMaskGate>), grid,       \
+                       dim3(256), 0, st, M, int(K), rpb, gY, ldg, Y, ldy, g_out, ldo, part,     \
+                       gate, ldgate)
   if (vec) {
-    if (use_gate) GCG_RELU_LAUNCH(4, true, true);
-    else if (mask) GCG_RELU_LAUNCH(4, true, false);
-    else GCG_RELU_LAUNCH(4, false, false);
+    if (mask == kMaskGate) { GCG_PASS_LAUNCH(4, kMaskGate); }
+    else if (mask == kMaskY) { GCG_PASS_LAUNCH(4, kMaskY); }
+    else { GCG_PASS_LAUNCH(4, kMaskNone); }
   } else {
-    if (use_gate) GCG_RELU_LAUNCH(1, true, true);
-    else if (mask) GCG_RELU_LAUNCH(1, true, false);
-    else GCG_RELU_LAUNCH(1, false, false);
+    if (mask == kMaskGate) { GCG_PASS_LAUNCH(1, kMaskGate); }
+    else if (mask == kMaskY) { GCG_PASS_LAUNCH(1, kMaskY); }
+    else { GCG_PASS_LAUNCH(1, kMaskNone); }
   }
-#undef GCG_RELU_LAUNCH
+#undef GCG_PASS_LAUNCH
   GCG_HIP_CHECK(hipGetLastError());
   if (bias_grad != nullptr) {
     hipLaunchKernelGGL(column_sum_kernel, dim3(static_cast<unsigned>((K + 63) / 64)), dim3(1024),
@@ -603,8 +500,8 @@ gcg_status gcg_relu_backward_f32(int64_t M, int64_t K, const float* gY, int64_t 
                                  const float* Y, int64_t ldy, float* g_out, int64_t ldo,
                                  float* bias_grad, void* workspace, size_t workspace_bytes,
                                  gcg_stream_t stream) {
-  return relu_colsum("gcg_relu_backward_f32", true, M, K, gY, ldg, Y, ldy, g_out, ldo, bias_grad,
-                     workspace, workspace_bytes, stream);
+  return rectify_backward("gcg_relu_backward_f32", kMaskY, nullptr, M, K, gY, ldg, Y, ldy, nullptr,
+                          0, g_out, ldo, bias_grad, workspace, workspace_bytes, stream);
 }
 
 gcg_status gcg_relu_backward_gate_f32(int64_t M, int64_t K, const float* gY, int64_t ldg,
@@ -613,8 +510,9 @@ gcg_status gcg_relu_backward_gate_f32(int64_t M, int64_t K, const float* gY, int
                                       size_t workspace_bytes, gcg_stream_t stream) {
   if (M > 0 && K > 0 && gate == nullptr)
     return fail(GCG_ERR_INVALID_ARG, "gcg_relu_backward_gate_f32: gate is NULL");
-  return relu_colsum("gcg_relu_backward_gate_f32", true, M, K, gY, ldg, nullptr, 0, g_out, ldo,
-                     bias_grad, workspace, workspace_bytes, stream, gate, ldgate);
+  return rectify_backward("gcg_relu_backward_gate_f32", kMaskGate, nullptr, M, K, gY, ldg, nullptr,
+                          0, gate, ldgate, g_out, ldo, bias_grad, workspace, workspace_bytes,
+                          stream);
 }
 
 gcg_status gcg_dropout_relu_backward_f32(int64_t M, int64_t K, const float* gY, int64_t ldg,
@@ -623,62 +521,18 @@ gcg_status gcg_dropout_relu_backward_f32(int64_t M, int64_t K, const float* gY, 
                                          size_t workspace_bytes, uint32_t threshold, float scale,
                                          uint64_t seed, const int32_t* step_dev,
                                          uint32_t stream_id, int64_t row0, gcg_stream_t stream) {
-  const char* fn = "gcg_dropout_relu_backward_f32";
-  if (M < 0 || K < 0 || K > 64 * 4 * kReluMaxK4 || row0 < 0)
-    return fail(GCG_ERR_INVALID_ARG, "%s: bad sizes M=%lld K=%lld (K <= %d)", fn,
-                static_cast<long long>(M), static_cast<long long>(K), 64 * 4 * kReluMaxK4);
-  auto st = static_cast<hipStream_t>(stream);
-  if (M == 0 || K == 0) {  // as relu_colsum: an empty sum is zero
-    if (bias_grad != nullptr && K > 0)
-      GCG_HIP_CHECK(hipMemsetAsync(bias_grad, 0, sizeof(float) * K, st));
-    return GCG_OK;
-  }
-  if (gY == nullptr || g_out == nullptr || step_dev == nullptr)
-    return fail(GCG_ERR_INVALID_ARG, "%s: null operand", fn);
-  if (ldg < K || ldo < K) return fail(GCG_ERR_INVALID_ARG, "%s: ld < K", fn);
-  if (gate != nullptr && (ldgate < K || ldgate % 4 != 0 || !aligned(gate, 4)))
-    return fail(GCG_ERR_MISALIGNED, "%s: gate needs ldgate >= K, ldgate %% 4 == 0, 4-B base", fn);
-  if (!aligned(gY, 4) || !aligned(g_out, 4) || !aligned(step_dev, 4))
-    return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B aligned", fn);
-  const int64_t rpb = relu_rows_per_block(M);
-  const int64_t n_blocks = (M + rpb - 1) / rpb;
-  const size_t need = sizeof(float) * static_cast<size_t>(n_blocks) * K;
-  if (workspace == nullptr || workspace_bytes < need)  // the kernel always writes partials
-    return fail(GCG_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, need);
-  if (!aligned(workspace, 4)) return fail(GCG_ERR_MISALIGNED, "%s: workspace alignment", fn);
-  float* part = static_cast<float*>(workspace);
-  // the layouts relu_colsum vectorizes (the gate call passes gY as its Y)
-  const bool vec = ldg % 4 == 0 && ldo % 4 == 0 && aligned(gY, 16) && aligned(g_out, 16);
-  if (!vec && K > 64 * kReluMaxK4)
-    return fail(GCG_ERR_MISALIGNED, "%s: K > %d needs 16-B rows (ld %% 4 == 0)", fn,
-                64 * kReluMaxK4);
-  const DropKey d{static_cast<uint32_t>(seed & 0xffffffffu), static_cast<uint32_t>(seed >> 32),
-                  0u, stream_id, threshold, scale};
-  const dim3 grid(static_cast<unsigned>(n_blocks));
-#define GCG_DROP_RELU_LAUNCH(V, GT)                                                             \
-  hipLaunchKernelGGL((dropout_relu_backward_kernel<V, GT>), grid, dim3(256), 0, st, M, int(K),   \
-                     rpb, gY, ldg, g_out, ldo, part, gate, ldgate, d, step_dev, row0)
-  if (vec) {
-    if (gate != nullptr) GCG_DROP_RELU_LAUNCH(4, true);
-    else GCG_DROP_RELU_LAUNCH(4, false);
-  } else {
-    if (gate != nullptr) GCG_DROP_RELU_LAUNCH(1, true);
-    else GCG_DROP_RELU_LAUNCH(1, false);
-  }
-#undef GCG_DROP_RELU_LAUNCH
-  GCG_HIP_CHECK(hipGetLastError());
-  if (bias_grad != nullptr) {
-    hipLaunchKernelGGL(column_sum_kernel, dim3(static_cast<unsigned>((K + 63) / 64)), dim3(1024),
-                       0, st, n_blocks, int(K), part, bias_grad);
-    GCG_HIP_CHECK(hipGetLastError());
-  }
-  return GCG_OK;
+  const DropArgs drop{{static_cast<uint32_t>(seed & 0xffffffffu),
+                       static_cast<uint32_t>(seed >> 32), 0u, stream_id, threshold, scale},
+                      step_dev, row0};
+  return rectify_backward("gcg_dropout_relu_backward_f32", gate != nullptr ? kMaskGate : kMaskNone,
+                          &drop, M, K, gY, ldg, nullptr, 0, gate, ldgate, g_out, ldo, bias_grad,
+                          workspace, workspace_bytes, stream);
 }
 
 gcg_status gcg_column_sum_f32(int64_t M, int64_t K, const float* X, int64_t ldx, float* out,
                               void* workspace, size_t workspace_bytes, gcg_stream_t stream) {
-  return relu_colsum("gcg_column_sum_f32", false, M, K, X, ldx, nullptr, 0, nullptr, 0, out,
-                     workspace, workspace_bytes, stream);
+  return rectify_backward("gcg_column_sum_f32", kMaskNone, nullptr, M, K, X, ldx, nullptr, 0,
+                          nullptr, 0, nullptr, 0, out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -38,6 +38,8 @@ import torch
 
 from . import ops as _ops  # registers torch.ops.gcg.* (the compiled path)
 from ._native import GCG_ACT_NONE, GCG_ACT_RELU, call, load
+# _colsum: the bias gradients' column sums (sparse.colsum), under the name this module uses
+from .sparse import _ptr, _require_cuda, _stream_handle, colsum as _colsum, empty_dense
 
 MATHS = {"f32": 0, "bf16x6": 1}  # gcg_spmm.h GCG_MATH_F32 / GCG_MATH_BF16X6
 
@@ -65,7 +67,7 @@ def _ws_bytes(fn: str, N: int, K: int, math: int) -> int:
     if nb is None:
         nb = _WS_SIZES[key] = int(getattr(load(), fn)(N, K, math))
     return nb
-from .sparse import _ptr, _require_cuda, _stream_handle, column_sum, empty_dense
+
 
 FUSED_MAX_COLS = 1024
 ROWS_MAX_COLS = 4096
@@ -363,11 +365,6 @@ def _bias_on_side_stream(b: Optional[torch.Tensor]):
     with torch.cuda.stream(_side_stream(b.device)):
         ba = _SideBiasGrad.apply(b, slot)
     return ba, slot
-
-
-def _colsum(X: torch.Tensor) -> torch.Tensor:
-    """Bias gradient: deterministic HIP column sum (K <= 1024), else torch's reduction."""
-    return column_sum(X) if X.dim() == 2 and X.shape[1] <= 1024 else X.sum(dim=0)
 
 
 def _placeholder_grad(W: torch.Tensor, like: torch.Tensor) -> torch.Tensor:

@@ -29,7 +29,6 @@ weight gradients differ only by the order of the cross-rank sum.
 from __future__ import annotations
 
 import logging
-import math
 from typing import Optional
 
 import numpy as np
@@ -42,7 +41,7 @@ from . import sparse as gs
 from .distributed import (RowPartitionedCSR, TargetRows, host_is_symmetric,  # noqa: F401
                           local_targets)
 from .layers import _glorot_uniform, csr_matmul
-from .mlpconv import LasagneAdam, trainer_order
+from .mlpconv import LasagneAdam, check_labels, check_trainer_args, fit_loop, trainer_order
 
 log = logging.getLogger(__name__)
 
@@ -66,11 +65,7 @@ class GPUOps:
     @staticmethod
     def relu_backward(gY, gate, bias_grad=True):
         """Theano's rectify gradient (g, g/2, 0 for gate 2, 1, 0) + the bias gradient."""
-        if gY.shape[1] <= 1024:
-            return gs.relu_backward(gY if gY.stride(-1) == 1 else gY.contiguous(), gate=gate,
-                                    bias_grad=bias_grad)
-        g = gY * (gate.to(gY.dtype) * 0.5)
-        return g, (g.sum(dim=0) if bias_grad else None)
+        return gs.epilogue_backward(gY, gate, bias_grad)
 
     @staticmethod
     def scatter_rows(n_rows: int, rows: gs.RowSelection, g: torch.Tensor) -> torch.Tensor:
@@ -372,8 +367,8 @@ class RowPartitionedMLPCONV:
     1-D row partition: one process per GPU, every rank calls the same methods with the same
     host arguments (each keeps its block). Same constructor arguments as MLPCONV plus
     rank / world / group / exchange; the epoch loop, validation every report_k_epoch,
-    best-parameter restore, early stopping and the final dev evaluation follow MLPCONV.fit
-    (graphconvgeo_amd/mlpconv.py), with every loss and hit count all-reduced so that every rank
+    best-parameter restore, early stopping and the final dev evaluation are MLPCONV.fit's
+    (mlpconv.fit_loop), with every loss and hit count all-reduced so that every rank
     takes the same decisions. predict / predict_proba return the requested partition's rows on
     rank 0 (None on the other ranks); accuracy and score are global on every rank."""
 
@@ -386,18 +381,11 @@ class RowPartitionedMLPCONV:
                  order: str = "auto", rank: Optional[int] = None,
                  world: Optional[int] = None, group=None, exchange: str = "auto",
                  network_factory=None):
-        if dtype != "float32":
-            raise ValueError("the GPU path computes in float32 (mlpconv.py dtype='float32')")
+        check_trainer_args(dtype, complete_prob, loss_name, order)
         if drop_out:
             raise NotImplementedError("dropout is not built into the row-partitioned trainer; "
                                       "the single-GPU MLPCONV(drop_out=True) has it "
                                       "(graphconvgeo_amd.dropout)")
-        if complete_prob:
-            raise NotImplementedError("complete_prob (soft labels) is not on the graded path")
-        if loss_name != "log":
-            raise ValueError("only the 'log' (categorical cross-entropy) loss exists in the reference")
-        if order not in ("reference", "propagate_first", "auto"):
-            raise ValueError("order must be 'reference', 'propagate_first' or 'auto'")
         self.n_epochs = n_epochs
         self.batch_size = batch_size
         self.init_parameters = init_parameters
@@ -417,11 +405,7 @@ class RowPartitionedMLPCONV:
 
     def fit(self, X, train_indices, dev_indices, test_indices, Y, H):
         """mlpconv.py:152-318 over the row partition (full-batch epochs)."""
-        Y = np.asarray(Y)
-        if Y.ndim != 1 or not np.issubdtype(Y.dtype, np.integer):
-            raise ValueError("Y must be a 1-D integer label array (complete_prob is out of scope)")
-        if Y.size and int(Y.min()) < 0:
-            raise ValueError("labels must be >= 0 (class ids, data.py:399-432)")
+        Y = check_labels(Y)
         if self.hidden_layer_size is None:
             raise ValueError("hidden_layer_size is required")
         out_size = int(np.max(Y)) + 1
@@ -449,35 +433,13 @@ class RowPartitionedMLPCONV:
         self.params = net.params
         opt = net.make_optimizer()
         self.optimizer = opt
-        best_params, best_val_loss, best_val_acc, n_down = None, math.inf, 0.0, 0
-        for n in range(self.n_epochs):
-            loss, acc = net.train_step(opt)
-            rec = {"epoch": n, "train_loss": float(loss), "train_acc": float(acc)}
-            if n % self.report_k_epoch == 0:
-                l_val, a_val = (float(x) for x in net.evaluate("dev"))
-                rec.update(val_loss=l_val, val_acc=a_val)
-                if l_val < best_val_loss:
-                    best_val_loss, best_val_acc, n_down = l_val, a_val, 0
-                    best_params = [p.detach().clone() for p in self.params]
-                else:
-                    n_down += 1
-                log.info("epoch %d ,train_loss %s ,acc %s ,val_loss %s ,acc %s,best_val_acc %s",
-                         n, rec["train_loss"], rec["train_acc"], l_val, a_val, best_val_acc)
-                self.history.append(rec)
-                if n_down > self.early_stopping_max_down:
-                    log.info("validation results went down. early stopping ...")
-                    break
-            else:
-                self.history.append(rec)
-        if best_params is not None:
-            with torch.no_grad():
-                for p, b in zip(self.params, best_params):
-                    p.copy_(b)
+        # the epochs, then the dev evaluation with the restored best parameters (mlpconv.py:316-318)
+        self.best_dev_loss, self.best_dev_acc = fit_loop(
+            lambda: net.train_step(opt), lambda: net.evaluate("dev"), self.params, self.history,
+            self.n_epochs, self.report_k_epoch, self.early_stopping_max_down)
         if self.model_file and self.rank == 0:
             torch.save([p.detach().cpu() for p in self.params], self.model_file)
             self.model_path = self.model_file
-        l_val, a_val = net.evaluate("dev")  # final dev evaluation, mlpconv.py:316-318
-        self.best_dev_loss, self.best_dev_acc = float(l_val), float(a_val)
         log.info("Best dev acc: %f", self.best_dev_acc)
         return self
 

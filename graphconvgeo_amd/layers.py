@@ -114,6 +114,25 @@ def _upload_cached(cache: dict, x, device) -> gs.DeviceCSR:
     return dev
 
 
+def _row_selection(target_indices, device) -> Optional[gs.RowSelection]:
+    """target_indices (None, an index array or a RowSelection) as the kernels take it."""
+    if target_indices is None or isinstance(target_indices, gs.RowSelection):
+        return target_indices
+    return gs.RowSelection(target_indices, device)
+
+
+def _init_affine(layer: nn.Module, W, b, rng) -> None:
+    """layer.W [num_inputs, num_units] (Glorot-uniform unless given) and layer.b (a constant
+    unless given; None: no bias) as parameters on layer.device."""
+    w = _glorot_uniform(layer.num_inputs, layer.num_units, rng) if W is None else W
+    layer.W = nn.Parameter(_as_tensor(w, (layer.num_inputs, layer.num_units), layer.device))
+    if b is None:
+        layer.b = None
+    else:
+        bb = np.full(layer.num_units, float(b), np.float32) if np.isscalar(b) else b
+        layer.b = nn.Parameter(_as_tensor(bb, (layer.num_units,), layer.device))
+
+
 def _as_device_csr(m, device) -> gs.DeviceCSR:
     if isinstance(m, gs.DeviceCSR):
         return m
@@ -153,22 +172,7 @@ class _CSRMatMul(torch.autograd.Function):
         A, rows = ctx.A, ctx.rows
         (gate,) = ctx.saved_tensors
         want_bias = ctx.has_bias and ctx.needs_input_grad[1]
-        if ctx.drop is not None:
-            # the mask regenerated, Theano's rectify gradient and the bias gradient in one
-            # pass (gcg_dropout_relu_backward_f32; gate None: no rectify)
-            g, g_bias = _drop.dropout_relu_backward(gY, ctx.drop, gate=gate,
-                                                    bias_grad=want_bias)
-        elif gate is not None and gY.shape[1] <= 1024:
-            # Theano rectify gradient and bias gradient in one pass (gcg_relu_backward_gate_f32)
-            g, g_bias = gs.relu_backward(gY.contiguous() if gY.stride(-1) != 1 else gY,
-                                         gate=gate, bias_grad=want_bias)
-        elif gate is None:
-            g = gY
-            g_bias = (gs.column_sum(gY) if gY.shape[1] <= 1024 else gY.sum(dim=0)) \
-                if want_bias else None
-        else:
-            g = gY * (gate.to(gY.dtype) * 0.5)
-            g_bias = g.sum(dim=0) if want_bias else None
+        g, g_bias = gs.epilogue_backward(gY, gate, want_bias, ctx.drop)
         g_Z = None
         if ctx.needs_input_grad[0] and ctx.bf16:
             # the gradient rounded once (after the rectify backward; the bias gradient above read
@@ -176,16 +180,7 @@ class _CSRMatMul(torch.autograd.Function):
             T = A.rows_transpose(rows) if rows is not None else A.transpose()
             g_Z = gs.spmm(T, gs.to_bf16_rows(g), mode=ctx.mode)
         elif ctx.needs_input_grad[0]:
-            if rows is not None:
-                # (A[rows])^T . g: one SpMM over the targets' nonzeros (sparse.rows_transpose),
-                # equal to A^T . inc_subtensor(zeros, rows, g) (mlpconv.py:94, Theano's grad)
-                # within fp32 rounding
-                # (a row-padded g -- C = 930 columns in 960-float rows -- is passed as is:
-                # .contiguous() would copy it and lose the padding the 16-B gathers use)
-                g_Z = gs.spmm(A.rows_transpose(rows), g if g.stride(-1) == 1 else g.contiguous(),
-                              mode=ctx.mode)
-            else:
-                g_Z = A.tmatmul(g if g.stride(-1) == 1 else g.contiguous(), mode=ctx.mode)
+            g_Z = gs.transposed_matmul(A, g, rows, ctx.mode)
         return g_Z, g_bias, None, None, None, None, None, None
 
 
@@ -279,13 +274,7 @@ class GraphConvLayer(nn.Module):
         # H^T for the backward: H itself when H is symmetric (declared by its builder, or found
         # so by DeviceCSR.check_symmetric at the first backward), else the built transpose
         self.H = _as_device_csr(H, self.device)
-        w = _glorot_uniform(self.num_inputs, self.num_units, rng) if W is None else W
-        self.W = nn.Parameter(_as_tensor(w, (self.num_inputs, self.num_units), self.device))
-        if b is None:
-            self.b = None
-        else:
-            bb = np.full(self.num_units, float(b), np.float32) if np.isscalar(b) else b
-            self.b = nn.Parameter(_as_tensor(bb, (self.num_units,), self.device))
+        _init_affine(self, W, b, rng)
         self.fused_act, self.post = _resolve_nonlinearity(nonlinearity)
         self.mode = mode
         self.require_sparse_input = require_sparse_input
@@ -314,10 +303,7 @@ class GraphConvLayer(nn.Module):
             Z = csr_matmul(self._sparse_input(input), self.W, mode=self.mode)  # S.dot(X, W)
         else:
             Z = dense.matmul(input, self.W)  # T.dot(h, W), mlpconv.py:88 (dW: split-K MFMA)
-        rows = None
-        if target_indices is not None:
-            rows = target_indices if isinstance(target_indices, gs.RowSelection) else \
-                gs.RowSelection(target_indices, self.device)
+        rows = _row_selection(target_indices, self.device)
         drop = self._dropout_spec(deterministic)
         if drop is not None:
             if self.post is not None:
@@ -388,8 +374,7 @@ class _TransformPropagate(torch.autograd.Function):
                 gW = dense.gemm_tn(P, g)
         if ctx.needs_input_grad[0]:
             GW = dense.gemm_nt(g, ctx.proj.bwd.get(W, False))  # g . W^T over the target rows
-            T = H.rows_transpose(rows) if rows is not None else None
-            gh = gs.spmm(T, GW, mode=mode) if T is not None else H.tmatmul(GW, mode=mode)
+            gh = gs.transposed_matmul(H, GW, rows, mode)
         return gh, gW, gb, None, None, None, None, None
 
 
@@ -424,10 +409,7 @@ class ConvolutionDenseLayer(GraphConvLayer):
 
     def propagate(self, input, target_indices=None) -> torch.Tensor:
         """(H . h)[target_indices] -- the K-wide SpMM of the propagate-first order."""
-        rows = None
-        if target_indices is not None:
-            rows = target_indices if isinstance(target_indices, gs.RowSelection) else \
-                gs.RowSelection(target_indices, self.device)
+        rows = _row_selection(target_indices, self.device)
         return csr_matmul(self.H, input, None, None, rows, self.mode,
                           gather_dtype=self.gather_dtype)
 
@@ -444,10 +426,7 @@ class ConvolutionDenseLayer(GraphConvLayer):
                 and self.gather_dtype == "float32"
                 and self.fused_act is None and self.num_units > self.num_inputs
                 and torch.is_grad_enabled()):
-            rows = None
-            if target_indices is not None:
-                rows = target_indices if isinstance(target_indices, gs.RowSelection) else \
-                    gs.RowSelection(target_indices, self.device)
+            rows = _row_selection(target_indices, self.device)
             if torch.compiler.is_compiling():  # the registered twin (graphconvgeo_amd.ops)
                 Y = _ops.transform_propagate(input, self.W, self.b, self.H, rows, self.mode)
                 return self.post(Y) if self.post is not None else Y
@@ -481,13 +460,7 @@ class SparseInputDenseLayer(nn.Module):
         self.device = torch.device(device)
         self.num_inputs = in_features if in_features is not None else _num_inputs(incoming)
         self.num_units = int(num_units)
-        w = _glorot_uniform(self.num_inputs, self.num_units, rng) if W is None else W
-        self.W = nn.Parameter(_as_tensor(w, (self.num_inputs, self.num_units), self.device))
-        if b is None:
-            self.b = None
-        else:
-            bb = np.full(self.num_units, float(b), np.float32) if np.isscalar(b) else b
-            self.b = nn.Parameter(_as_tensor(bb, (self.num_units,), self.device))
+        _init_affine(self, W, b, rng)
         self.fused_act, self.post = _resolve_nonlinearity(nonlinearity)
         self.mode = mode
         self._cache = {}

@@ -341,14 +341,7 @@ class MLP:
                 if last:  # the loss the reference reports: the last batch's, with the penalty
                     loss, acc = ce.detach() + self._penalty(), a
                 g = h.grad if h.grad.stride(-1) == 1 else h.grad.contiguous()
-                if self.add_hidden:
-                    if K <= 1024:
-                        g, db1 = gs.relu_backward(g, gate=gate)
-                    else:  # the one-pass kernel's column limit, as layers._CSRMatMul
-                        g = g * (gate.to(g.dtype) * 0.5)
-                        db1 = g.sum(dim=0)
-                else:
-                    db1 = dense._colsum(g)
+                g, db1 = gs.epilogue_backward(g, gate, True)  # gate None: no hidden rectify
                 opt.prepare()
                 if self._w1_update is not None:
                     self._w1_update(self, b, g, l1, l2)

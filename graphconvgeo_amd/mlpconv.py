@@ -115,6 +115,65 @@ def trainer_order(order: str, in_size: int, n_classes: int) -> str:
     return "reference"
 
 
+def check_trainer_args(dtype, complete_prob, loss_name, order) -> None:
+    """The constructor arguments the full-batch trainers share (MLPCONV and the row-partitioned
+    dist_train.RowPartitionedMLPCONV)."""
+    if dtype != "float32":
+        raise ValueError("the GPU path computes in float32 (mlpconv.py dtype='float32')")
+    if complete_prob:
+        raise NotImplementedError("complete_prob (soft labels) is not on the graded path")
+    if loss_name != "log":
+        raise ValueError("only the 'log' (categorical cross-entropy) loss exists in the reference")
+    if order not in ("reference", "propagate_first", "auto"):
+        raise ValueError("order must be 'reference', 'propagate_first' or 'auto'")
+
+
+def check_labels(Y) -> np.ndarray:
+    """fit's Y as a 1-D array of class ids >= 0."""
+    Y = np.asarray(Y)
+    if Y.ndim != 1 or not np.issubdtype(Y.dtype, np.integer):
+        raise ValueError("Y must be a 1-D integer label array (complete_prob is out of scope)")
+    if Y.size and int(Y.min()) < 0:
+        raise ValueError("labels must be >= 0 (class ids, data.py:399-432)")
+    return Y
+
+
+def fit_loop(train_step, evaluate, params, history, n_epochs, report_k_epoch,
+             early_stopping_max_down):
+    """The reference's epoch loop (mlpconv.py:290-318) for both full-batch trainers, so that
+    every rank of the partitioned one takes the decisions the single-GPU one takes.
+    train_step() -> (loss, acc) runs one epoch; evaluate() -> (loss, acc) is the dev set's,
+    called every report_k_epoch epochs. A strictly lower dev loss snapshots `params`; more than
+    early_stopping_max_down validations without one stop the loop. One record per epoch is
+    appended to `history`. At the end the best snapshot (if any) is copied back into `params`
+    and the dev set is evaluated once more (mlpconv.py:316-318): that (loss, acc) is returned."""
+    best_params, best_val_loss, best_val_acc, n_down = None, math.inf, 0.0, 0
+    for n in range(n_epochs):
+        loss, acc = train_step()
+        rec = {"epoch": n, "train_loss": float(loss), "train_acc": float(acc)}
+        history.append(rec)
+        if n % report_k_epoch != 0:
+            continue
+        l_val, a_val = (float(x) for x in evaluate())
+        rec.update(val_loss=l_val, val_acc=a_val)
+        if l_val < best_val_loss:
+            best_val_loss, best_val_acc, n_down = l_val, a_val, 0
+            best_params = [p.detach().clone() for p in params]
+        else:
+            n_down += 1
+        log.info("epoch %d ,train_loss %s ,acc %s ,val_loss %s ,acc %s,best_val_acc %s",
+                 n, rec["train_loss"], rec["train_acc"], l_val, a_val, best_val_acc)
+        if n_down > early_stopping_max_down:
+            log.info("validation results went down. early stopping ...")
+            break
+    if best_params is not None:
+        with torch.no_grad():
+            for p, b in zip(params, best_params):
+                p.copy_(b)
+    l_val, a_val = evaluate()
+    return float(l_val), float(a_val)
+
+
 class MLPCONV:
     def __init__(self, n_epochs=10, batch_size=1000, init_parameters=None, complete_prob=False,
                  add_hidden=True, regul_coefs=(5e-5, 5e-5), save_results=False,
@@ -123,18 +182,13 @@ class MLPCONV:
                  dtype="float32", device="cuda", seed: Optional[int] = None, mode: str = "auto",
                  model_file: Optional[str] = None, report_k_epoch: int = 10,
                  order: str = "auto", use_graph: bool = False, gather_dtype: str = "float32"):
-        if dtype != "float32":
-            raise ValueError("the GPU path computes in float32 (mlpconv.py dtype='float32')")
+        check_trainer_args(dtype, complete_prob, loss_name, order)
         self.drop_out = bool(drop_out)
         if self.drop_out:
             drop_out_hid, drop_out_in = dropout_coefs  # mlpconv.py:155
             for p in (drop_out_hid, drop_out_in):
                 if not 0.0 <= float(p) < 1.0:
                     raise ValueError("dropout_coefs must be in [0, 1)")
-        if complete_prob:
-            raise NotImplementedError("complete_prob (soft labels) is not on the graded path")
-        if loss_name != "log":
-            raise ValueError("only the 'log' (categorical cross-entropy) loss exists in the reference")
         self.n_epochs = n_epochs
         self.batch_size = batch_size  # unused by the reference's full-batch loop, kept for API
         self.init_parameters = init_parameters
@@ -153,8 +207,6 @@ class MLPCONV:
         # resolved by trainer_order). Neither order is bitwise to the reference's P (the
         # projection runs on MFMA in its own k order); both meet the same float64 bars
         # (tests/test_config3_gpu.py).
-        if order not in ("reference", "propagate_first", "auto"):
-            raise ValueError("order must be 'reference', 'propagate_first' or 'auto'")
         self.order = order
         # "bfloat16": the four H-products of a step (two forward, two backward) gather a
         # bfloat16 copy of their dense operand (layers.GATHER_DTYPES); X . W1 and X^T . dZ1 stay
@@ -267,11 +319,7 @@ class MLPCONV:
     # -- reference API ------------------------------------------------------------------
     def fit(self, X, train_indices, dev_indices, test_indices, Y, H):
         """mlpconv.py:152-318 (full-batch epochs, validation every report_k_epoch)."""
-        Y = np.asarray(Y)
-        if Y.ndim != 1 or not np.issubdtype(Y.dtype, np.integer):
-            raise ValueError("Y must be a 1-D integer label array (complete_prob is out of scope)")
-        if Y.size and int(Y.min()) < 0:
-            raise ValueError("labels must be >= 0 (class ids, data.py:399-432)")
+        Y = check_labels(Y)
         out_size = int(np.max(Y)) + 1
         in_size = X.shape[1]
         if self.hidden_layer_size is None:
@@ -289,32 +337,15 @@ class MLPCONV:
         opt = LasagneAdam(self.params, lr=4e-3, beta1=0.9, beta2=0.999, epsilon=1e-8)
         self.optimizer = opt
         train_step = self._make_train_step(opt, y_train)
-        best_params, best_val_loss, best_val_acc, n_down = None, math.inf, 0.0, 0
-        for n in range(self.n_epochs):
-            loss, acc = train_step()
-            rec = {"epoch": n, "train_loss": float(loss), "train_acc": float(acc)}
-            if n % self.report_k_epoch == 0:
-                with torch.no_grad():
-                    l_val, a_val = self._loss_acc(self.rows["dev"], y_dev)
-                l_val, a_val = float(l_val), float(a_val)
-                rec.update(val_loss=l_val, val_acc=a_val)
-                if l_val < best_val_loss:
-                    best_val_loss, best_val_acc, n_down = l_val, a_val, 0
-                    best_params = [p.detach().clone() for p in self.params]
-                else:
-                    n_down += 1
-                log.info("epoch %d ,train_loss %s ,acc %s ,val_loss %s ,acc %s,best_val_acc %s",
-                         n, rec["train_loss"], rec["train_acc"], l_val, a_val, best_val_acc)
-                self.history.append(rec)
-                if n_down > self.early_stopping_max_down:
-                    log.info("validation results went down. early stopping ...")
-                    break
-            else:
-                self.history.append(rec)
-        if best_params is not None:
+
+        def evaluate():
             with torch.no_grad():
-                for p, b in zip(self.params, best_params):
-                    p.copy_(b)
+                return self._loss_acc(self.rows["dev"], y_dev)
+
+        # the epochs, then the dev evaluation with the restored best parameters (mlpconv.py:316-318)
+        self.best_dev_loss, self.best_dev_acc = fit_loop(
+            train_step, evaluate, self.params, self.history, self.n_epochs, self.report_k_epoch,
+            self.early_stopping_max_down)
         if self.model_file:
             # the reference always pickles the best params (mlpconv.py:310-313); here only on
             # request: model_file="reference" writes its path, anything else is a path
@@ -325,10 +356,6 @@ class MLPCONV:
             log.info("storing best parameters in %s ...", path)
             torch.save([p.detach().cpu() for p in self.params], path)
             self.model_path = path
-        # final dev evaluation with the restored best parameters (mlpconv.py:316-318)
-        with torch.no_grad():
-            l_val, a_val = self._loss_acc(self.rows["dev"], y_dev)
-        self.best_dev_loss, self.best_dev_acc = float(l_val), float(a_val)
         log.info("Best dev acc: %f", self.best_dev_acc)
         return self
 

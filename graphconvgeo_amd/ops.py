@@ -91,19 +91,8 @@ def spmm_csr_backward_op(gY: Tensor, gate: Tensor, csr: int, rows: int, mode: st
     sel = _rows_arg(rows)
     if gY.stride(-1) != 1:
         gY = gY.contiguous()
-    K = gY.shape[1]
-    if has_gate and K <= 1024:
-        g, g_bias = gs.relu_backward(gY, gate=gate, bias_grad=want_bias)
-    elif not has_gate:
-        g = gY
-        g_bias = (gs.column_sum(gY) if K <= 1024 else gY.sum(dim=0)) if want_bias else None
-    else:
-        g = gY * (gate.to(gY.dtype) * 0.5)
-        g_bias = g.sum(dim=0) if want_bias else None
-    g_Z = None
-    if want_z:
-        g_Z = gs.spmm(A.rows_transpose(sel), g, mode=mode) if sel is not None else \
-            A.tmatmul(g, mode=mode)
+    g, g_bias = gs.epilogue_backward(gY, gate if has_gate else None, want_bias)
+    g_Z = gs.transposed_matmul(A, g, sel, mode) if want_z else None
     empty = gY.new_empty(0)
     return (g_Z if g_Z is not None else empty), (g_bias if g_bias is not None else empty)
 
@@ -174,7 +163,7 @@ def _(A, B, scale):
 @torch.library.custom_op(f"{LIB}::column_sum", mutates_args=())
 def column_sum_op(X: Tensor) -> Tensor:
     """X.sum(0), deterministic (gcg_column_sum_f32, K <= 1024): the bias gradients."""
-    return gs.column_sum(X) if X.shape[1] <= 1024 else X.sum(dim=0)
+    return gs.colsum(X)
 
 
 @column_sum_op.register_fake

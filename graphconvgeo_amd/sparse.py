@@ -915,6 +915,45 @@ def relu_backward(gY: torch.Tensor, Y: Optional[torch.Tensor] = None,
     return out, db
 
 
+def colsum(X: torch.Tensor) -> torch.Tensor:
+    """X.sum(0): column_sum up to the one-pass kernel's 1024 columns, torch's sum beyond."""
+    return column_sum(X) if X.dim() == 2 and X.shape[1] <= 1024 else X.sum(dim=0)
+
+
+def epilogue_backward(gY: torch.Tensor, gate: Optional[torch.Tensor], want_bias: bool,
+                      drop=None):
+    """(g, db): the backward of drop(act(A . Z + b)[rows]) up to the product, the one statement
+    of the rule for the layers, the registered op and the trainers. gate: the rectify gate
+    bytes of the forward (None: no rectify, g = gY); db = the column sums of g (None unless
+    want_bias). drop (a dropout.DropoutSpec): the mask regenerated in the same pass
+    (dropout.dropout_relu_backward, at most 1024 columns). Up to 1024 columns the gate rule and
+    the sums are one kernel (relu_backward); beyond, Theano's 0.5 * g * (1 + sgn) from the gate
+    bytes (2 / 1 / 0) in torch."""
+    if drop is not None:
+        from . import dropout  # dropout imports this module
+        return dropout.dropout_relu_backward(gY, drop, gate=gate, bias_grad=want_bias)
+    if gate is None:
+        return gY, (colsum(gY) if want_bias else None)
+    if gY.shape[1] <= 1024:
+        return relu_backward(gY if gY.stride(-1) == 1 else gY.contiguous(), gate=gate,
+                             bias_grad=want_bias)
+    g = gY * (gate.to(gY.dtype) * 0.5)
+    return g, (g.sum(dim=0) if want_bias else None)
+
+
+def transposed_matmul(A: DeviceCSR, g: torch.Tensor, rows: Optional[RowSelection] = None,
+                      mode: str = "auto") -> torch.Tensor:
+    """The gradient of (A . Z)[rows] with respect to Z. With rows, (A[rows])^T . g: one SpMM
+    over the targets' nonzeros (rows_transpose), equal to A^T . inc_subtensor(zeros, rows, g)
+    (mlpconv.py:94, Theano's grad) within fp32 rounding; without, A.tmatmul(g). A row-padded g
+    (C = 930 columns in 960-float rows) is passed as is: .contiguous() would copy it and lose
+    the padding the 16-B gathers use."""
+    g = g if g.stride(-1) == 1 else g.contiguous()
+    if rows is not None:
+        return spmm(A.rows_transpose(rows), g, mode=mode)
+    return A.tmatmul(g, mode=mode)
+
+
 def index_csr(idx: torch.Tensor, n_rows: int):
     """(seg_ptr, sorted_pos): CSR of an index list, stable (gcg_index_csr)."""
     _require_cuda(idx, "idx")
