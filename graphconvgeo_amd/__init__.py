@@ -13,9 +13,11 @@ Product modules (all compute runs in libgcg_spmm.so HIP kernels; no CPU fallback
   mlp          MLP mini-batch trainer (mlp.py:96-311) on the GPU, input_convolution (H * X)
   geo          k-d-tree region labels (kdtree.py), class medians, haversine, nearest class and
                geo_eval (mean / median km, Acc@161) on the GPU, data.py:399-419
+  mdn          the mixture-density location head (lang2loc.py): fused NLL + gradient, the
+               "mixture" prediction rule, NNModel_lang2loc (text -> lat/lon) on the GPU
   synth        seeded synthetic graphs / features for the BASELINE configs
 
-`MLP`, `input_convolution` and `DeviceCSR` are imported lazily from the package itself.
+`MLP`, `input_convolution`, `NNModel_lang2loc` and `DeviceCSR` are imported lazily from the package itself.
 """
 import os as _os
 
@@ -30,9 +32,10 @@ __version__ = "0.1.0"
 _os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "8")
 
 __all__ = ["sparse", "ops", "layers", "dense", "distributed", "dist_train", "graph", "mentions",
-           "mlpconv", "mlp", "geo", "synth", "MLP", "input_convolution", "DeviceCSR"]
+           "mlpconv", "mlp", "geo", "mdn", "synth", "MLP", "input_convolution", "NNModel_lang2loc",
+           "DeviceCSR"]
 
-_LAZY = {"MLP": "mlp", "input_convolution": "mlp", "DeviceCSR": "sparse"}
+_LAZY = {"MLP": "mlp", "input_convolution": "mlp", "NNModel_lang2loc": "mdn", "DeviceCSR": "sparse"}
 
 
 def __getattr__(name):

@@ -15,11 +15,12 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 # Translation units of libgcg_spmm.so: SpMM kernels + planner, the bf16-operand SpMM and its row
 # conversion, CSR utilities, graph build,
 # SpGEMM, MFMA dense projection + softmax/xent, Philox dropout, the mini-batch MLP's epoch
-# segmentation and W1 step, k-d-tree labels + geolocation metrics, error/version helpers.
+# segmentation and W1 step, k-d-tree labels + geolocation metrics, the mixture-density location
+# head, error/version helpers.
 # Compiled in parallel, linked into one shared library.
 SOURCES = [os.path.join(CSRC, f) for f in
            ("spmm.hip", "spmm_bf16.hip", "csr_ops.hip", "graph_build.hip", "spgemm.hip", "dense.hip", "dropout.hip",
-            "minibatch.hip", "geo.hip", "errors.cpp")]
+            "minibatch.hip", "geo.hip", "mdn.hip", "errors.cpp")]
 INTERNAL_HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "spmm_shared.h", "index_kernels.h",
                                                     "gemm_epilogue.inc", "philox.h",
                                                     "rectify_backward_pass.inc")]

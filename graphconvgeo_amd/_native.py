@@ -76,6 +76,14 @@ SIGNATURES = {
     "gcg_minibatch_w1_step_f32": (C.c_int, [_i64, _i64, _p, _p, _p, _p, _i64, _i64, _p, _p, _p,
                                             _p, _p, C.c_float, C.c_float, _p, C.c_float,
                                             C.c_float, C.c_float, _p]),
+    "gcg_minibatch_segment_dropout": (C.c_int, [_i64, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p,
+                                                _p, _p, _p, _p, _p, _p, C.c_size_t, C.c_uint32,
+                                                C.c_float, C.c_uint64, _p, C.c_uint32, _p]),
+    # the mixture-density location head (csrc/mdn.hip)
+    "gcg_mdn_nll_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _p, _p, _i64, _p, _p, _p, C.c_size_t,
+                                  _p]),
+    "gcg_mdn_unpack_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _p, _p, _p, _p]),
+    "gcg_mdn_predict_f32": (C.c_int, [_i64, _i64, _p, _i64, C.c_int, _p, _p, _p]),
     "gcg_csr_validate": (C.c_int, [_i64, _i64, _i64, _p, _p, _p, _p]),
     "gcg_index_csr": (C.c_int, [_i64, _p, _i64, _p, _p, _p, C.c_size_t, _psz, _p]),
     "gcg_scatter_add_rows_f32": (C.c_int, [_i64, _p, _p, _p, _i64, _i64, _p, _i64, _p]),

@@ -1,0 +1,410 @@
+// mdn.hip -- the mixture-density location head (reference lang2loc.py:143-244): a row of
+// 6 * C raw outputs read as a mixture of C bivariate Gaussians over (lat, lon). The fused
+// negative log-likelihood with its gradient, the reference's "mixture" / "pi" prediction rule,
+// and the transform of the raw outputs into (mus, sigmas, corxy, pis) the two are built from.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "common.h"
+
+using namespace gcg;
+
+namespace {
+
+constexpr int kMaxComp = 1024;
+constexpr float kLatScale = 90.0f, kLonScale = 180.0f, kSigmaScale = 10.0f;
+constexpr float kLog2Pi = 1.8378770664093453f;   // log(2 pi)
+constexpr float kInv2Pi = 0.15915494309189535f;  // 0.5 / pi
+
+// ---- the transforms of one component (lang2loc.py:143-160) ----------------------------------
+
+// softplus in its stable form: max(x, 0) + log1p(exp(-|x|)).
+__device__ __forceinline__ float softplus(float x) {
+  return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x)));
+}
+
+// The sigmoid, softplus's derivative, without overflow on either side.
+__device__ __forceinline__ float sigmoid(float x) {
+  const float t = expf(-fabsf(x));
+  return x >= 0.0f ? 1.0f / (1.0f + t) : t / (1.0f + t);
+}
+
+// rho = softsign(t) and 1 - rho^2 = (1 + 2|t|) / (1 + |t|)^2 from the raw value (no
+// cancellation as |rho| -> 1).
+struct Corr {
+  float rho, q, inv1;  // inv1 = 1 / (1 + |t|); d rho / d t = inv1^2
+};
+__device__ __forceinline__ Corr corr_of(float t) {
+  const float a = fabsf(t);
+  const float inv1 = 1.0f / (1.0f + a);
+  return Corr{t * inv1, (1.0f + 2.0f * a) * (inv1 * inv1), inv1};
+}
+
+// Butterfly reductions over the wave: the same order for every lane, every launch.
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
+  return v;
+}
+
+// The two halves of a log-sum-exp, kept apart: logsumexp = max + log(sum), while a softmax
+// weight is exp(x - max) / sum -- formed from the sum, it does not inherit the rounding of
+// max + log(sum) at the magnitude of max (|e| reaches 1e4 where a sigma is small).
+struct Lse {
+  float max, sum;
+};
+
+// Of a lane's N values across the wave (inactive slots hold -inf).
+template <int N>
+__device__ __forceinline__ Lse wave_lse(const float (&x)[N]) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < N; ++i) m = fmaxf(m, x[i]);
+  m = wave_max(m);
+  float s = 0.0f;
+#pragma unroll
+  for (int i = 0; i < N; ++i) s = s + expf(x[i] - m);
+  return Lse{m, wave_sum(s)};
+}
+
+// A mean against its target: d = y - S tanh(x) and d mu / d x = S (1 - tanh(x)^2). The one
+// place that leaves float32: |mu| reaches 180, so mu rounded to float32 is off by up to 8e-6,
+// and y - mu amplifies that without bound as the mean closes in on its target -- which is where
+// training takes it. tanh and the difference are formed in double and rounded once.
+struct Mean {
+  float d, dmu;
+};
+__device__ __forceinline__ Mean mean_of(float x, float S, float y) {
+  const double t = tanh(static_cast<double>(x));
+  return Mean{static_cast<float>(static_cast<double>(y) - static_cast<double>(S) * t),
+              static_cast<float>(static_cast<double>(S) * (1.0 - t * t))};
+}
+
+// ---- NLL and gradient -----------------------------------------------------------------------
+
+// One wave per row; lane l owns the components l, l + 64, ... (N = ceil(C / 64) of them), so
+// each of the six planes is read coalesced. Pass 1 forms e_c (kept in registers), the
+// log-sum-exp gives the row's loss, pass 2 re-reads the row (cache-resident) and writes the
+// gradient of (upstream / B) * loss_r with respect to every raw output.
+template <int N>
+__global__ __launch_bounds__(kBlock) void mdn_nll_kernel(
+    int64_t B, int C, const float* __restrict__ O, int64_t ldo, const float* __restrict__ Y,
+    const float* __restrict__ scale_dev, float* __restrict__ dO, int64_t ldd,
+    float* __restrict__ loss_rows) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+  if (r >= B) return;
+  const float* o = O + r * ldo;
+  const float y1 = Y[2 * r], y2 = Y[2 * r + 1];
+
+  float lg[N], e[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int c = lane + i * kWave;
+    lg[i] = c < C ? o[5 * C + c] : -INFINITY;
+  }
+  const Lse lp = wave_lse<N>(lg);
+  const float log_sum_pi = logf(lp.sum);
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int c = lane + i * kWave;
+    e[i] = -INFINITY;
+    if (c < C) {
+      const float s1 = kSigmaScale * softplus(o[2 * C + c]);
+      const float s2 = kSigmaScale * softplus(o[3 * C + c]);
+      const Corr k = corr_of(o[4 * C + c]);
+      const float u1 = mean_of(o[c], kLatScale, y1).d / s1;
+      const float u2 = mean_of(o[C + c], kLonScale, y2).d / s2;
+      const float z = (u1 * u1 + u2 * u2) - 2.0f * k.rho * (u1 * u2);
+      e[i] = ((((-0.5f * z) / k.q - kLog2Pi) - (logf(s1) + logf(s2))) - 0.5f * logf(k.q)) +
+             ((lg[i] - lp.max) - log_sum_pi);
+    }
+  }
+  const Lse le = wave_lse<N>(e);
+  if (lane == 0 && loss_rows != nullptr) loss_rows[r] = -(le.max + logf(le.sum));
+  if (dO == nullptr) return;
+
+  const float up = (scale_dev != nullptr ? *scale_dev : 1.0f) / static_cast<float>(B);
+  float* g = dO + r * ldd;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int c = lane + i * kWave;
+    if (c < C) {
+      const float w = expf(e[i] - le.max) / le.sum;  // the component's responsibility
+      const float pi = expf(lg[i] - lp.max) / lp.sum;
+      const Mean m1 = mean_of(o[c], kLatScale, y1), m2 = mean_of(o[C + c], kLonScale, y2);
+      const float r1 = o[2 * C + c], r2 = o[3 * C + c];
+      const float s1 = kSigmaScale * softplus(r1), s2 = kSigmaScale * softplus(r2);
+      const Corr k = corr_of(o[4 * C + c]);
+      const float u1 = m1.d / s1, u2 = m2.d / s2;
+      const float z = (u1 * u1 + u2 * u2) - 2.0f * k.rho * (u1 * u2);
+      const float a1 = (u1 - k.rho * u2) / k.q, a2 = (u2 - k.rho * u1) / k.q;
+      // d e / d mu_i = a_i / s_i, d e / d s_i = (u_i a_i - 1) / s_i,
+      // d e / d rho = (u1 u2 + rho (1 - z / q)) / q; d loss / d e = -w
+      const float m = -(w * up);
+      g[c] = m * (a1 / s1) * m1.dmu;
+      g[C + c] = m * (a2 / s2) * m2.dmu;
+      g[2 * C + c] = m * ((u1 * a1 - 1.0f) / s1) * (kSigmaScale * sigmoid(r1));
+      g[3 * C + c] = m * ((u2 * a2 - 1.0f) / s2) * (kSigmaScale * sigmoid(r2));
+      g[4 * C + c] = m * ((u1 * u2 + k.rho * (1.0f - z / k.q)) / k.q) * (k.inv1 * k.inv1);
+      g[5 * C + c] = (pi - w) * up;
+    }
+  }
+}
+
+// *loss = (sum of rows in a fixed order) / B: thread t adds rows t, t + 256, ... in order, then
+// a halving tree over the 256 partials. One workgroup, no atomics.
+__global__ __launch_bounds__(256) void mdn_mean_kernel(int64_t B, const float* __restrict__ rows,
+                                                       float* __restrict__ loss) {
+  __shared__ float part[256];
+  float s = 0.0f;
+  for (int64_t r = threadIdx.x; r < B; r += 256) s = s + rows[r];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (static_cast<int>(threadIdx.x) < h) part[threadIdx.x] = part[threadIdx.x] + part[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *loss = part[0] / static_cast<float>(B);
+}
+
+// ---- the four arrays of f_predict -----------------------------------------------------------
+
+// One wave per row: mus [B, 2, C], sigmas [B, 2, C], corxy [B, C], pis [B, C], contiguous, with
+// the device functions the two kernels beside it use.
+template <int N>
+__global__ __launch_bounds__(kBlock) void mdn_unpack_kernel(
+    int64_t B, int C, const float* __restrict__ O, int64_t ldo, float* __restrict__ mus,
+    float* __restrict__ sigmas, float* __restrict__ corxy, float* __restrict__ pis) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+  if (r >= B) return;
+  const float* o = O + r * ldo;
+  float lg[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int c = lane + i * kWave;
+    lg[i] = c < C ? o[5 * C + c] : -INFINITY;
+  }
+  const Lse lp = wave_lse<N>(lg);
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int c = lane + i * kWave;
+    if (c < C) {
+      mus[(2 * r) * C + c] = kLatScale * tanhf(o[c]);
+      mus[(2 * r + 1) * C + c] = kLonScale * tanhf(o[C + c]);
+      sigmas[(2 * r) * C + c] = kSigmaScale * softplus(o[2 * C + c]);
+      sigmas[(2 * r + 1) * C + c] = kSigmaScale * softplus(o[3 * C + c]);
+      corxy[r * C + c] = corr_of(o[4 * C + c]).rho;
+      pis[r * C + c] = expf(lg[i] - lp.max) / lp.sum;
+    }
+  }
+}
+
+// ---- prediction -----------------------------------------------------------------------------
+
+// The better of two (score, index) candidates: the higher score, the lower index on a tie.
+__device__ __forceinline__ void take_better(float& s, int& i, float s2, int i2) {
+  if (s2 > s || (s2 == s && i2 < i)) {
+    s = s2;
+    i = i2;
+  }
+}
+
+// One workgroup per row. Six planes of the row are staged in LDS once:
+//   mu1, mu2, a1 = sqrt(h) / s1, a2 = sqrt(h) / s2 with h = 0.5 / (1 - rho^2), rho,
+//   w = pi * (0.5 / pi) / (s1 s2) * sqrt(1 / (1 - rho^2))
+// so that the density of component k at x is w_k * exp(-(v1^2 + v2^2 - 2 rho v1 v2)),
+// v_i = (x_i - mu_i) a_i -- the reference's expression with the factor -0.5 / (1 - rho^2) moved
+// inside the square. Thread t scores the candidates t, t + 256, ...: the sum over k ascending,
+// every lane reading the same k (an LDS broadcast). method 1 scores a candidate by its logit.
+__global__ __launch_bounds__(kBlock) void mdn_predict_kernel(
+    int64_t B, int C, const float* __restrict__ O, int64_t ldo, int method,
+    int32_t* __restrict__ idx, float* __restrict__ latlon) {
+  extern __shared__ float lds[];
+  __shared__ float best_s[kWavesPerBlock];
+  __shared__ int best_i[kWavesPerBlock];
+  float* mu1 = lds;
+  float* mu2 = lds + C;
+  float* a1 = lds + 2 * C;
+  float* a2 = lds + 3 * C;
+  float* rho = lds + 4 * C;
+  float* wgt = lds + 5 * C;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+  for (int64_t r = blockIdx.x; r < B; r += gridDim.x) {
+    const float* o = O + r * ldo;
+    // the softmax of the logits over the workgroup: max, then the sum
+    float m = -INFINITY;
+    for (int c = tid; c < C; c += kBlock) m = fmaxf(m, o[5 * C + c]);
+    m = wave_max(m);
+    if (lane == 0) best_s[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(best_s[0], best_s[1]), fmaxf(best_s[2], best_s[3]));
+    __syncthreads();
+    float s = 0.0f;
+    for (int c = tid; c < C; c += kBlock) s = s + expf(o[5 * C + c] - m);
+    s = wave_sum(s);
+    if (lane == 0) best_s[wave] = s;
+    __syncthreads();
+    const float sum_pi = (best_s[0] + best_s[1]) + (best_s[2] + best_s[3]);
+    for (int c = tid; c < C; c += kBlock) {
+      const float s1 = kSigmaScale * softplus(o[2 * C + c]);
+      const float s2 = kSigmaScale * softplus(o[3 * C + c]);
+      const Corr k = corr_of(o[4 * C + c]);
+      const float qi = 1.0f / k.q;
+      const float sh = sqrtf(0.5f * qi);
+      mu1[c] = kLatScale * tanhf(o[c]);
+      mu2[c] = kLonScale * tanhf(o[C + c]);
+      a1[c] = sh / s1;
+      a2[c] = sh / s2;
+      rho[c] = k.rho;
+      wgt[c] = method == 0 ? expf(o[5 * C + c] - m) / sum_pi * kInv2Pi * ((1.0f / s1) * (1.0f / s2)) * sqrtf(qi)
+                           : o[5 * C + c];
+    }
+    __syncthreads();
+    float bs = -INFINITY;
+    int bi = INT32_MAX;
+    for (int c = tid; c < C; c += kBlock) {
+      float score;
+      if (method == 0) {
+        const float x1 = mu1[c], x2 = mu2[c];
+        score = 0.0f;
+        for (int k = 0; k < C; ++k) {
+          const float v1 = (x1 - mu1[k]) * a1[k], v2 = (x2 - mu2[k]) * a2[k];
+          const float z = (v1 * v1 + v2 * v2) - 2.0f * rho[k] * (v1 * v2);
+          score = score + wgt[k] * expf(-z);
+        }
+      } else {
+        score = wgt[c];
+      }
+      take_better(bs, bi, score, c);  // ascending c: a later equal score never replaces
+    }
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1)
+      take_better(bs, bi, __shfl_xor(bs, off), __shfl_xor(bi, off));
+    if (lane == 0) {
+      best_s[wave] = bs;
+      best_i[wave] = bi;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < kWavesPerBlock; ++w) take_better(bs, bi, best_s[w], best_i[w]);
+      // every score NaN leaves no winner: component 0, in bounds
+      const int win = (bi >= 0 && bi < C) ? bi : 0;
+      if (idx != nullptr) idx[r] = win;
+      latlon[2 * r] = mu1[win];
+      latlon[2 * r + 1] = mu2[win];
+    }
+    __syncthreads();  // the planes and the slots are rewritten for the next row
+  }
+}
+
+gcg_status check_layout(const char* fn, int64_t B, int64_t C, int64_t ldo) {
+  if (B < 0 || B > INT32_MAX || C < 1 || C > kMaxComp)
+    return fail(GCG_ERR_INVALID_ARG, "%s: bad sizes B=%lld C=%lld (1 <= C <= %d)", fn,
+                static_cast<long long>(B), static_cast<long long>(C), kMaxComp);
+  if (ldo < 6 * C)
+    return fail(GCG_ERR_INVALID_ARG, "%s: row stride %lld < 6 C = %lld", fn,
+                static_cast<long long>(ldo), static_cast<long long>(6 * C));
+  return GCG_OK;
+}
+
+unsigned row_blocks(int64_t B) {
+  return static_cast<unsigned>((B + kWavesPerBlock - 1) / kWavesPerBlock);
+}
+
+// N = components per lane, rounded up to a power of two (register arrays of that size).
+#define GCG_MDN_DISPATCH(C, LAUNCH)      \
+  do {                                   \
+    if ((C) <= 64) LAUNCH(1);            \
+    else if ((C) <= 128) LAUNCH(2);      \
+    else if ((C) <= 256) LAUNCH(4);      \
+    else if ((C) <= 512) LAUNCH(8);      \
+    else LAUNCH(16);                     \
+  } while (0)
+
+}  // namespace
+
+extern "C" {
+
+gcg_status gcg_mdn_nll_f32(int64_t B, int64_t C, const float* O, int64_t ldo, const float* Y,
+                           const float* scale_dev, float* dO, int64_t ldd, float* loss_rows,
+                           float* loss, void* workspace, size_t workspace_bytes,
+                           gcg_stream_t stream) {
+  const char* fn = "gcg_mdn_nll_f32";
+  if (gcg_status s = check_layout(fn, B, C, ldo)) return s;
+  if (dO != nullptr && ldd < 6 * C)
+    return fail(GCG_ERR_INVALID_ARG, "%s: gradient row stride %lld < 6 C", fn,
+                static_cast<long long>(ldd));
+  if (B == 0) return GCG_OK;
+  if (O == nullptr || Y == nullptr || loss == nullptr)
+    return fail(GCG_ERR_INVALID_ARG, "%s: NULL operand", fn);
+  if (!aligned(O, 4) || !aligned(Y, 4) || !aligned(dO, 4) || !aligned(loss_rows, 4) ||
+      !aligned(loss, 4) || !aligned(scale_dev, 4) || !aligned(workspace, 4))
+    return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B aligned", fn);
+  float* rows = loss_rows;
+  if (rows == nullptr) {  // the row losses the mean is taken of need a home
+    if (workspace == nullptr || workspace_bytes < sizeof(float) * static_cast<size_t>(B))
+      return fail(GCG_ERR_WORKSPACE, "%s: without loss_rows the workspace holds them: %zu < %zu "
+                  "bytes", fn, workspace_bytes, sizeof(float) * static_cast<size_t>(B));
+    rows = static_cast<float*>(workspace);
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int c = static_cast<int>(C);
+#define GCG_MDN_NLL(N)                                                                        \
+  hipLaunchKernelGGL((mdn_nll_kernel<N>), dim3(row_blocks(B)), dim3(kBlock), 0, st, B, c, O, \
+                     ldo, Y, scale_dev, dO, ldd, rows)
+  GCG_MDN_DISPATCH(C, GCG_MDN_NLL);
+#undef GCG_MDN_NLL
+  GCG_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(mdn_mean_kernel, dim3(1), dim3(256), 0, st, B, rows, loss);
+  GCG_HIP_CHECK(hipGetLastError());
+  return GCG_OK;
+}
+
+gcg_status gcg_mdn_unpack_f32(int64_t B, int64_t C, const float* O, int64_t ldo, float* mus,
+                              float* sigmas, float* corxy, float* pis, gcg_stream_t stream) {
+  const char* fn = "gcg_mdn_unpack_f32";
+  if (gcg_status s = check_layout(fn, B, C, ldo)) return s;
+  if (B == 0) return GCG_OK;
+  if (O == nullptr || mus == nullptr || sigmas == nullptr || corxy == nullptr || pis == nullptr)
+    return fail(GCG_ERR_INVALID_ARG, "%s: NULL operand", fn);
+  if (!aligned(O, 4) || !aligned(mus, 4) || !aligned(sigmas, 4) || !aligned(corxy, 4) ||
+      !aligned(pis, 4))
+    return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B aligned", fn);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int c = static_cast<int>(C);
+#define GCG_MDN_UNPACK(N)                                                                       \
+  hipLaunchKernelGGL((mdn_unpack_kernel<N>), dim3(row_blocks(B)), dim3(kBlock), 0, st, B, c, O, \
+                     ldo, mus, sigmas, corxy, pis)
+  GCG_MDN_DISPATCH(C, GCG_MDN_UNPACK);
+#undef GCG_MDN_UNPACK
+  GCG_HIP_CHECK(hipGetLastError());
+  return GCG_OK;
+}
+
+gcg_status gcg_mdn_predict_f32(int64_t B, int64_t C, const float* O, int64_t ldo, int method,
+                               int32_t* idx, float* latlon, gcg_stream_t stream) {
+  const char* fn = "gcg_mdn_predict_f32";
+  if (gcg_status s = check_layout(fn, B, C, ldo)) return s;
+  if (method != 0 && method != 1)
+    return fail(GCG_ERR_INVALID_ARG, "%s: method %d is neither 0 (mixture) nor 1 (pi)", fn, method);
+  if (B == 0) return GCG_OK;
+  if (O == nullptr || latlon == nullptr) return fail(GCG_ERR_INVALID_ARG, "%s: NULL operand", fn);
+  if (!aligned(O, 4) || !aligned(idx, 4) || !aligned(latlon, 4))
+    return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B aligned", fn);
+  const unsigned grid = static_cast<unsigned>(std::min<int64_t>(B, int64_t{1} << 16));
+  hipLaunchKernelGGL(mdn_predict_kernel, dim3(grid), dim3(kBlock),
+                     sizeof(float) * 6 * static_cast<size_t>(C), static_cast<hipStream_t>(stream),
+                     B, static_cast<int>(C), O, ldo, method, idx, latlon);
+  GCG_HIP_CHECK(hipGetLastError());
+  return GCG_OK;
+}
+
+}  // extern "C"

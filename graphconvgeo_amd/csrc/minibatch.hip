@@ -6,6 +6,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"
+#include "philox.h"
 
 using namespace gcg;
 
@@ -55,6 +56,45 @@ __global__ __launch_bounds__(kBlock) void mb_expand_kernel(
       const int32_t c = indices[s + j];
       key[e] = (c >= 0 && c < F) ? kb + static_cast<uint32_t>(c) : sentinel;
       payload[e] = pos | __float_as_uint(vals[s + j]);
+    }
+  }
+}
+
+// mb_expand_kernel with input dropout (gcg_minibatch_segment_dropout): every selected entry is
+// masked by the keep rule of philox.h -- logical row = the row's id in X, logical column = its
+// column, step = *step_dev + the batch's index in the call -- and the masked value goes both
+// into the sort payload (so ent_val is masked for the W1 step) and into vals_drop at the
+// entry's own CSR slot (so the existing forward reads it). A row is in at most one batch of an
+// epoch's order, so no slot is written twice.
+__global__ __launch_bounds__(kBlock) void mb_expand_dropout_kernel(
+    int64_t n_rows, int64_t F, const int32_t* __restrict__ indptr,
+    const int32_t* __restrict__ indices, const float* __restrict__ vals,
+    const int32_t* __restrict__ perm, int64_t n_sel, int64_t batch, int64_t nnz_sel,
+    uint32_t sentinel, const int32_t* __restrict__ sel_ptr, uint32_t* __restrict__ key,
+    uint64_t* __restrict__ payload, DropKey d, const int32_t* __restrict__ step_dev,
+    float* __restrict__ vals_drop) {
+  const uint32_t step0 = static_cast<uint32_t>(*step_dev);
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wstride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+  for (int64_t p = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6); p < n_sel;
+       p += wstride) {
+    const int32_t r = perm[p];
+    if (r < 0 || r >= n_rows) continue;
+    const int32_t s = indptr[r];
+    const int32_t n = indptr[r + 1] - s;
+    const int64_t base = sel_ptr[p];
+    const int64_t b = p / batch;
+    const uint32_t kb = static_cast<uint32_t>(b * F);
+    const uint64_t pos = static_cast<uint64_t>(p % batch) << 32;
+    d.step = step0 + static_cast<uint32_t>(b);
+    for (int32_t j = lane; j < n; j += kWave) {
+      const int64_t e = base + j;
+      if (e < 0 || e >= nnz_sel) break;  // a caller's nnz_sel below the rows' real total
+      const int32_t c = indices[s + j];
+      const float v = drop_element(d, r, c, vals[s + j]);
+      vals_drop[s + j] = v;
+      key[e] = (c >= 0 && c < F) ? kb + static_cast<uint32_t>(c) : sentinel;
+      payload[e] = pos | __float_as_uint(v);
     }
   }
 }
@@ -318,31 +358,14 @@ __global__ __launch_bounds__(kBlock) void w1_step_kernel(
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-gcg_status gcg_minibatch_segment_sizes(int64_t n_sel, int64_t batch, int64_t n_cols,
-                                       int64_t nnz_sel, int64_t* seg_capacity,
-                                       size_t* workspace_bytes) {
-  SegLayout L;
-  if (gcg_status s = seg_layout("gcg_minibatch_segment_sizes", n_sel, batch, n_cols, nnz_sel, &L))
-    return s;
-  if (seg_capacity != nullptr) *seg_capacity = L.seg_cap;
-  if (workspace_bytes != nullptr) {
-    if (gcg_status s = seg_layout_tmp("gcg_minibatch_segment_sizes", n_sel, nnz_sel, &L)) return s;
-    *workspace_bytes = L.total;
-  }
-  return GCG_OK;
-}
-
-gcg_status gcg_minibatch_segment(int64_t n_rows, int64_t n_cols, const int32_t* indptr,
-                                 const int32_t* indices, const float* vals, const int32_t* perm,
-                                 int64_t n_sel, int64_t batch, int64_t nnz_sel,
-                                 int32_t* batch_seg_ptr, int32_t* seg_col, int32_t* seg_ptr,
-                                 int32_t* ent_pos, float* ent_val, void* workspace,
-                                 size_t workspace_bytes, gcg_stream_t stream) {
-  const char* fn = "gcg_minibatch_segment";
+// Both segmentation calls: `drop` NULL is gcg_minibatch_segment, otherwise the expand pass masks
+// (mb_expand_dropout_kernel); every other launch is shared.
+gcg_status segment_impl(const char* fn, int64_t n_rows, int64_t n_cols, const int32_t* indptr,
+                        const int32_t* indices, const float* vals, const int32_t* perm,
+                        int64_t n_sel, int64_t batch, int64_t nnz_sel, int32_t* batch_seg_ptr,
+                        int32_t* seg_col, int32_t* seg_ptr, int32_t* ent_pos, float* ent_val,
+                        void* workspace, size_t workspace_bytes, gcg_stream_t stream,
+                        const DropKey* drop, const int32_t* step_dev, float* vals_drop) {
   if (n_rows < 0 || n_rows >= INT32_MAX)
     return fail(GCG_ERR_INVALID_ARG, "%s: bad n_rows", fn);
   SegLayout L;
@@ -386,11 +409,15 @@ gcg_status gcg_minibatch_segment(int64_t n_rows, int64_t n_cols, const int32_t* 
   GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, len, sel_ptr,
                                                  static_cast<int>(n_sel + 1), st));
   const int64_t row_blocks = (n_sel + kWavesPerBlock - 1) / kWavesPerBlock;
-  hipLaunchKernelGGL(mb_expand_kernel,
-                     dim3(static_cast<unsigned>(std::min<int64_t>(std::max<int64_t>(row_blocks, 1),
-                                                                  1 << 20))),
-                     dim3(kBlock), 0, st, n_rows, n_cols, indptr, indices, vals, perm, n_sel, batch,
-                     nnz_sel, sentinel, sel_ptr, key_in, pay_in);
+  const dim3 expand_grid(
+      static_cast<unsigned>(std::min<int64_t>(std::max<int64_t>(row_blocks, 1), 1 << 20)));
+  if (drop == nullptr)
+    hipLaunchKernelGGL(mb_expand_kernel, expand_grid, dim3(kBlock), 0, st, n_rows, n_cols, indptr,
+                       indices, vals, perm, n_sel, batch, nnz_sel, sentinel, sel_ptr, key_in, pay_in);
+  else
+    hipLaunchKernelGGL(mb_expand_dropout_kernel, expand_grid, dim3(kBlock), 0, st, n_rows, n_cols,
+                       indptr, indices, vals, perm, n_sel, batch, nnz_sel, sentinel, sel_ptr,
+                       key_in, pay_in, *drop, step_dev, vals_drop);
   GCG_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(mb_tail_kernel, dim3(64), dim3(256), 0, st, sel_ptr, n_sel, nnz_sel, sentinel,
                      key_in, pay_in);
@@ -412,6 +439,56 @@ gcg_status gcg_minibatch_segment(int64_t n_rows, int64_t n_cols, const int32_t* 
                      seg_key, n_seg, batch_seg_ptr);
   GCG_HIP_CHECK(hipGetLastError());
   return GCG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+gcg_status gcg_minibatch_segment_sizes(int64_t n_sel, int64_t batch, int64_t n_cols,
+                                       int64_t nnz_sel, int64_t* seg_capacity,
+                                       size_t* workspace_bytes) {
+  SegLayout L;
+  if (gcg_status s = seg_layout("gcg_minibatch_segment_sizes", n_sel, batch, n_cols, nnz_sel, &L))
+    return s;
+  if (seg_capacity != nullptr) *seg_capacity = L.seg_cap;
+  if (workspace_bytes != nullptr) {
+    if (gcg_status s = seg_layout_tmp("gcg_minibatch_segment_sizes", n_sel, nnz_sel, &L)) return s;
+    *workspace_bytes = L.total;
+  }
+  return GCG_OK;
+}
+
+gcg_status gcg_minibatch_segment(int64_t n_rows, int64_t n_cols, const int32_t* indptr,
+                                 const int32_t* indices, const float* vals, const int32_t* perm,
+                                 int64_t n_sel, int64_t batch, int64_t nnz_sel,
+                                 int32_t* batch_seg_ptr, int32_t* seg_col, int32_t* seg_ptr,
+                                 int32_t* ent_pos, float* ent_val, void* workspace,
+                                 size_t workspace_bytes, gcg_stream_t stream) {
+  return segment_impl("gcg_minibatch_segment", n_rows, n_cols, indptr, indices, vals, perm, n_sel,
+                      batch, nnz_sel, batch_seg_ptr, seg_col, seg_ptr, ent_pos, ent_val, workspace,
+                      workspace_bytes, stream, nullptr, nullptr, nullptr);
+}
+
+gcg_status gcg_minibatch_segment_dropout(int64_t n_rows, int64_t n_cols, const int32_t* indptr,
+                                         const int32_t* indices, const float* vals,
+                                         const int32_t* perm, int64_t n_sel, int64_t batch,
+                                         int64_t nnz_sel, int32_t* batch_seg_ptr, int32_t* seg_col,
+                                         int32_t* seg_ptr, int32_t* ent_pos, float* ent_val,
+                                         float* vals_drop, void* workspace, size_t workspace_bytes,
+                                         uint32_t threshold, float scale, uint64_t seed,
+                                         const int32_t* step_dev, uint32_t stream_id,
+                                         gcg_stream_t stream) {
+  const char* fn = "gcg_minibatch_segment_dropout";
+  if (step_dev == nullptr || (nnz_sel > 0 && vals_drop == nullptr))
+    return fail(GCG_ERR_INVALID_ARG, "%s: NULL buffer", fn);
+  if (!aligned(step_dev, 4) || !aligned(vals_drop, 4))
+    return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B aligned", fn);
+  const DropKey d{static_cast<uint32_t>(seed & 0xffffffffu), static_cast<uint32_t>(seed >> 32), 0u,
+                  stream_id, threshold, scale};
+  return segment_impl(fn, n_rows, n_cols, indptr, indices, vals, perm, n_sel, batch, nnz_sel,
+                      batch_seg_ptr, seg_col, seg_ptr, ent_pos, ent_val, workspace, workspace_bytes,
+                      stream, &d, step_dev, vals_drop);
 }
 
 gcg_status gcg_minibatch_w1_step_f32(int64_t F, int64_t K, float* W, float* m, float* v,

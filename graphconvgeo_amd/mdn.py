@@ -1,0 +1,443 @@
+"""The mixture-density location head -- the reference's lang2loc.py (text to lat/lon).
+
+A sparse bag-of-words goes through a tanh hidden layer to 6 * ncomp outputs, read as a mixture
+of ncomp bivariate Gaussians over (lat, lon) (lang2loc.py:143-160) and trained by negative
+log-likelihood (lang2loc.py:166-196); a prediction is the component mean where the mixture
+density is highest (lang2loc.py:198-244).
+
+  unpack_params     (mus, sigmas, corxy, pis) of a raw output      gcg_mdn_unpack_f32
+  mdn_nll           the mean NLL, differentiable in the output     gcg_mdn_nll_f32 (forward and
+                                                                   gradient in one launch)
+  mdn_predict       the "mixture" / "pi" rule -> (n, 2) lat/lon    gcg_mdn_predict_f32
+  geo_eval_latlon   lang2loc.geo_latlon_eval (mean / median km, Acc@161) on geo.geo_eval
+  NNModel_lang2loc  the reference's class: constructor arguments, fit, predict
+
+The layout of a raw output row is the reference's output.reshape(-1, 6, ncomp): six planes of
+ncomp columns (means lat, lon; sigmas lat, lon; correlation; mixture logits). The transforms
+and the stable forms they are evaluated in are stated in include/gcg_spmm.h.
+"""
+from __future__ import annotations
+
+import logging
+from typing import Optional
+
+import numpy as np
+import scipy.sparse as sps
+import torch
+
+from . import dense, geo
+from . import sparse as gs
+from ._native import GCG_ACT_NONE, call
+from .dropout import DropoutStream, draw_seed, make_spec
+from .layers import _as_tensor, _glorot_uniform, _upload_cached
+from .mlp import BatchSegments, n_batches, plan_epoch, w1_step
+from .mlpconv import LasagneAdam
+from .sparse import _ptr, _stream_handle
+
+log = logging.getLogger(__name__)
+
+MAX_COMPONENTS = 1024
+METHODS = {"mixture": 0, "pi": 1}
+
+
+def _ld(t: torch.Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
+
+
+def _check_output(O: torch.Tensor, n_comp: int) -> torch.Tensor:
+    n_comp = int(n_comp)
+    if not 1 <= n_comp <= MAX_COMPONENTS:
+        raise ValueError(f"n_comp must be in [1, {MAX_COMPONENTS}], got {n_comp}")
+    gs._require_cuda(O, "O")
+    if O.dtype != torch.float32 or O.dim() != 2 or O.shape[1] != 6 * n_comp:
+        raise ValueError(f"O must be a float32 [B, {6 * n_comp}] tensor (6 planes of n_comp)")
+    return O if O.stride(1) == 1 else O.contiguous()
+
+
+def unpack_params(O: torch.Tensor, n_comp: int):
+    """lang2loc.unpack_params: (mus [B, 2, C], sigmas [B, 2, C], corxy [B, C], pis [B, C]) of a
+    raw output O [B, 6 C], float32 device tensors."""
+    O = _check_output(O, n_comp)
+    B, C, dev = O.shape[0], int(n_comp), O.device
+    mus = torch.empty((B, 2, C), dtype=torch.float32, device=dev)
+    sigmas = torch.empty((B, 2, C), dtype=torch.float32, device=dev)
+    corxy = torch.empty((B, C), dtype=torch.float32, device=dev)
+    pis = torch.empty((B, C), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        call("gcg_mdn_unpack_f32", B, C, _ptr(O), _ld(O), _ptr(mus), _ptr(sigmas), _ptr(corxy),
+             _ptr(pis), _stream_handle(dev))
+    return mus, sigmas, corxy, pis
+
+
+def _targets(Y: torch.Tensor, B: int, dev) -> torch.Tensor:
+    gs._require_cuda(Y, "Y")
+    if Y.dtype != torch.float32 or Y.shape != (B, 2) or Y.device != dev:
+        raise ValueError(f"Y must be a float32 [{B}, 2] tensor (lat, lon) on O's device")
+    return Y.contiguous()
+
+
+def nll_forward_backward(O: torch.Tensor, Y: torch.Tensor, want_grad: bool = True,
+                         scale: Optional[torch.Tensor] = None, want_rows: bool = False):
+    """(loss, dO, loss_rows) from one gcg_mdn_nll_f32 call: the mean NLL (device scalar), the
+    gradient of scale * loss with respect to O (None unless want_grad; scale: a device scalar,
+    default 1) and the per-row losses (None unless want_rows)."""
+    if O.dim() != 2 or O.shape[1] % 6 or O.shape[0] == 0:
+        raise ValueError("O must be [B, 6 * n_comp] with B >= 1")
+    C = O.shape[1] // 6
+    O = _check_output(O, C)
+    B, dev = O.shape[0], O.device
+    Y = _targets(Y, B, dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    rows = torch.empty(B, dtype=torch.float32, device=dev)  # also the home of the mean's input
+    dO = gs.empty_dense(B, 6 * C, dev) if want_grad else None
+    if scale is not None:
+        scale = scale.reshape(1).to(torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        call("gcg_mdn_nll_f32", B, C, _ptr(O), _ld(O), _ptr(Y), _ptr(scale), _ptr(dO),
+             _ld(dO) if dO is not None else 0, _ptr(rows), _ptr(loss), None, 0,
+             _stream_handle(dev))
+    return loss, dO, (rows if want_rows else None)
+
+
+class _MdnNll(torch.autograd.Function):
+    """The forward launch already writes the gradient of the mean (upstream 1); backward scales
+    it by the upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, O, Y):
+        loss, dO, _ = nll_forward_backward(O, Y, want_grad=ctx.needs_input_grad[0])
+        ctx.dO = dO
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.dO * g, None
+
+
+def mdn_nll(O: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+    """lang2loc.nll_loss on a raw output O [B, 6 C] and targets Y [B, 2] (lat, lon): the mean
+    over the rows of -logsumexp_c(log pi_c + log N(y; mu_c, sigma_c, rho_c)), differentiable
+    in O. Device scalar."""
+    return _MdnNll.apply(O, Y)
+
+
+def mdn_predict(O: torch.Tensor, n_comp: int, method: str = "mixture", return_index: bool = False):
+    """lang2loc.pred: per row the component mean that maximises the mixture density
+    ("mixture") or belongs to the largest pi ("pi"). Returns latlon [B, 2] float32 (device), and
+    the chosen component [B] int32 with return_index."""
+    if method not in METHODS:
+        raise ValueError(f"prediction method must be one of {sorted(METHODS)}")
+    O = _check_output(O, n_comp)
+    B, dev = O.shape[0], O.device
+    latlon = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    idx = torch.empty(B, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        call("gcg_mdn_predict_f32", B, int(n_comp), _ptr(O), _ld(O), METHODS[method], _ptr(idx),
+             _ptr(latlon), _stream_handle(dev))
+    return (latlon, idx) if return_index else latlon
+
+
+def geo_eval_latlon(pred_latlon, locs, earth_radius_km: float = geo.EARTH_RADIUS_KM,
+                    threshold_km: float = 161.0, device=None):
+    """lang2loc.geo_latlon_eval (lang2loc.py:81-98): (mean km, median km, Acc@161) of the
+    haversine distance from every true location to its predicted coordinate -- geo.geo_eval with
+    the predictions as the "medians" and arange as the classes."""
+    if device is None and isinstance(pred_latlon, torch.Tensor) and pred_latlon.is_cuda:
+        device = pred_latlon.device
+    classes = torch.arange(len(pred_latlon), dtype=torch.int64)
+    return geo.geo_eval(classes, locs, pred_latlon, earth_radius_km, threshold_km, device=device)
+
+
+class NNModel_lang2loc:
+    """lang2loc.NNModel_lang2loc (lang2loc.py:100-463) with every product and the loss on the GPU.
+
+    Network: tanh(X.W1 + b1) (SparseInputDenseLayer) then the linear h.W2 + b2 with 6 * ncomp
+    units; GlorotUniform weights drawn W1 then W2 (the input dropout's seed first when dropout
+    is on), zero biases. Loss: mdn_nll plus regul_coef * 0.5 * (sum|W1| + sum W1^2) when
+    regul_coef is truthy -- only the hidden layer is penalised: lang2loc.py:315-318 assign the
+    output layer's penalty and then overwrite it, and this follows what runs. Adam, lr 1e-3.
+
+    One epoch (lang2loc.py:426-451): shuffled batches with the tail dropped
+    (mlp.iterate_minibatch_indices); the reported train loss is the mean of the batch losses
+    (each before its update), accumulated on the device; the dev loss is the mean over the
+    unshuffled dev batches with the tail dropped, computed as one deterministic forward over the
+    first (n_dev // B) * B dev rows. Strict `l_val < best` keeps the parameters, otherwise a
+    counter runs and training stops when it exceeds early_stopping_max_down; the best parameters
+    are restored. No host synchronisation between an epoch's first and last batch.
+
+    Step: forward over the batch's rows (plan-less SpMM), tanh, the output GEMM, gcg_mdn_nll_f32
+    (loss and gradient in one launch), the backward GEMMs, the tanh backward g * (1 - h^2) with
+    its column sums, then one pass over W1 (mlp.w1_step) on the batch's segments.
+
+    Deviations: drop_out=True (with dropout_coef > 0) masks X in training only -- the reference
+    evaluates validation and prediction with its single training graph, dropout on
+    (lang2loc.py:300, 328-329); here both are deterministic. predict covers every row (the
+    reference's driver drops the tail batch, lang2loc.py:604-609). sqerror=True, a truthy
+    reload and dense inputs are refused; autoencoder is accepted and unused, as there.
+    """
+
+    def __init__(self, n_epochs=10, batch_size=1000, regul_coef=1e-6, input_size=None,
+                 output_size=None, hid_size=100, drop_out=False, dropout_coef=0.5,
+                 early_stopping_max_down=10, dtype="float32", autoencoder=100,
+                 input_sparse=False, reload=False, ncomp=100, sqerror=False, dataset_name="",
+                 init_parameters=None, device="cuda"):
+        if sqerror:
+            raise NotImplementedError("sqerror (the squared-error regressor) is not built")
+        if reload:
+            raise NotImplementedError("reload (a pickled model file) is not built")
+        if dtype != "float32":
+            raise ValueError("the GPU path computes in float32 (lang2loc.py dtype='float32')")
+        if not 1 <= int(ncomp) <= MAX_COMPONENTS:
+            raise ValueError(f"ncomp must be in [1, {MAX_COMPONENTS}]")
+        if int(hid_size) < 1:
+            raise ValueError("hid_size must be at least 1")
+        if drop_out and not 0.0 <= float(dropout_coef) < 1.0:
+            raise ValueError("dropout_coef must be in [0, 1)")
+        self.n_epochs = n_epochs
+        self.batch_size = int(batch_size)
+        self.regul_coef = regul_coef
+        self.hid_size = int(hid_size)
+        self.drop_out = bool(drop_out)
+        self.dropout_coef = float(dropout_coef)
+        self.early_stopping_max_down = early_stopping_max_down
+        self.dtype = dtype
+        self.input_size = input_size
+        self.output_size = output_size
+        self.autoencoder = autoencoder
+        self.sparse = input_sparse
+        self.reload = False
+        self.n_bigaus_comp = int(ncomp)
+        self.sqerror = False
+        self.dataset_name = dataset_name
+        self.init_parameters = init_parameters
+        self.device = torch.device(device)
+        self.history = []
+        self._inputs = {}
+
+    # -- model --------------------------------------------------------------------------
+    @property
+    def _drops(self) -> bool:
+        return self.drop_out and self.dropout_coef > 0  # lang2loc.py:280
+
+    def _build(self, in_size: int):
+        K, N, dev = self.hid_size, 6 * self.n_bigaus_comp, self.device
+        init = self.init_parameters
+        if init is not None and len(init) != 4:
+            raise ValueError("init_parameters must be [W1, b1, W2, b2], as "
+                             "lasagne.layers.get_all_param_values gives them")
+
+        def param(x, shape):
+            return torch.nn.Parameter(_as_tensor(x, shape, dev), requires_grad=False)
+
+        # Lasagne draws in construction order: the dropout layer's seed, then W1, then W2
+        self._stream = DropoutStream(draw_seed(), 0, dev) if self._drops else None
+        self._drop = make_spec(self._stream, self.dropout_coef) if self._drops else None
+        self.W1 = param(_glorot_uniform(in_size, K) if init is None else init[0], (in_size, K))
+        self.b1 = param(np.zeros(K, np.float32) if init is None else init[1], (K,))
+        self.W2 = param(_glorot_uniform(K, N) if init is None else init[2],
+                        (K, N)).requires_grad_(True)
+        self.b2 = param(np.zeros(N, np.float32) if init is None else init[3],
+                        (N,)).requires_grad_(True)
+        self.params = [self.W1, self.b1, self.W2, self.b2]
+        self.in_size = in_size
+        self._proj = dense.Projection()
+        # W1's Adam state lives beside it (updated inside the W1 step kernel)
+        self.optimizer = LasagneAdam(self.params[1:], lr=1e-3, beta1=0.9, beta2=0.999,
+                                     epsilon=1e-8)
+        self.m1 = torch.zeros_like(self.W1)
+        self.v1 = torch.zeros_like(self.W1)
+
+    def _penalty_coefs(self):
+        """(l1, l2) of W1: 0.5 shares of regul_coef (lang2loc.py:310-318), 0 when falsy."""
+        c = float(self.regul_coef) if self.regul_coef else 0.0
+        return c * 0.5, c * 0.5
+
+    def _penalty(self) -> Optional[torch.Tensor]:
+        if not self.regul_coef:
+            return None
+        return dense.l1l2_penalty([self.W1], [self._penalty_coefs()])
+
+    def _input(self, X) -> gs.DeviceCSR:
+        if isinstance(X, gs.DeviceCSR):
+            Xd = X
+        elif sps.issparse(X):
+            Xd = _upload_cached(self._inputs, X.tocsr() if X.format != "csr" else X, self.device)
+        else:
+            raise ValueError("Input for this layer must be sparse")
+        if hasattr(self, "in_size") and Xd.n_cols != self.in_size:
+            raise ValueError(f"X has {Xd.n_cols} columns, the model {self.in_size}")
+        return Xd
+
+    def _hidden(self, X: gs.DeviceCSR, vals: torch.Tensor, rows: Optional[torch.Tensor],
+                n_out: int) -> torch.Tensor:
+        """tanh(X[rows].W1 + b1) with X's values read from `vals`: the plan-less SpMM (one wave
+        per output row, no activation in its epilogue), then tanh in place. rows: int32 device
+        row ids, range-checked by the caller; None: the first n_out rows are all of X."""
+        K, dev = self.hid_size, self.device
+        h = gs.empty_dense(n_out, K, dev)
+        if n_out == 0:
+            return h
+        with torch.cuda.device(dev):
+            call("gcg_spmm_csr_f32_gate", X.n_rows, X.n_cols, X.nnz, _ptr(X.indptr),
+                 _ptr(X.indices), _ptr(vals), _ptr(self.W1), K, K, _ptr(h), _ld(h),
+                 _ptr(self.b1), GCG_ACT_NONE, _ptr(rows), n_out, None, 0, _stream_handle(dev))
+        return h.tanh_()
+
+    @torch.no_grad()
+    def _output(self, Xd: gs.DeviceCSR, n_rows: Optional[int] = None) -> torch.Tensor:
+        """The deterministic raw output of the first n_rows rows (default: all)."""
+        n = Xd.n_rows if n_rows is None else n_rows
+        rows = None
+        if n != Xd.n_rows:
+            rows = torch.arange(n, dtype=torch.int32, device=self.device)
+        h = self._hidden(Xd, Xd.data, rows, n)
+        return self._proj.matmul(h, self.W2.detach(), self.b2.detach())
+
+    @torch.no_grad()
+    def _evaluate(self, Xd: gs.DeviceCSR, Y: torch.Tensor) -> torch.Tensor:
+        """f_val over the unshuffled batches with the tail dropped (lang2loc.py:433-438): every
+        batch has B rows, so the mean of the batch means is the mean over the first
+        (n // B) * B rows -- one forward."""
+        n = n_batches(Xd.n_rows, self.batch_size) * self.batch_size
+        loss, _, _ = nll_forward_backward(self._output(Xd, n), Y[:n], want_grad=False)
+        pen = self._penalty()
+        return loss if pen is None else loss + pen
+
+    # -- training -----------------------------------------------------------------------
+    def _coords(self, Y, n: int, name: str) -> torch.Tensor:
+        Y = np.asarray(Y)
+        if Y.ndim != 2 or Y.shape != (n, 2):
+            raise ValueError(f"{name} must have shape ({n}, 2) [lat, lon], got {Y.shape}")
+        return torch.from_numpy(np.ascontiguousarray(Y, dtype=np.float32)).to(self.device)
+
+    def _prepare_epoch(self, order) -> None:
+        """Host half of an epoch: the order checked to be a permutation, cut into whole batches
+        and uploaded; its targets gathered once; the runs each segmentation call takes."""
+        n = self.Xd.n_rows
+        order = np.asarray(order)
+        if order.ndim != 1 or order.size != n or \
+                not np.array_equal(np.sort(order), np.arange(n)):
+            # a row in two batches would also share one slot of the dropped values
+            raise ValueError(f"an epoch's order must be a permutation of the {n} training rows")
+        perm, self._runs, self._n_batches = plan_epoch(order, self._indptr_host, self.batch_size)
+        self._perm = torch.from_numpy(perm.astype(np.int32)).to(self.device)
+        self._y_epoch = self._y_train.index_select(0, self._perm.to(torch.int64))
+
+    @torch.no_grad()
+    def _run_batches(self) -> torch.Tensor:
+        """Device half of an epoch: every batch's step, no host synchronisation. Returns the
+        mean of the batch losses (penalty included) as a device scalar."""
+        B, dev = self.batch_size, self.device
+        X, opt = self.Xd, self.optimizer
+        l1, l2 = self._penalty_coefs()
+        total = torch.zeros((), dtype=torch.float32, device=dev)
+        for first, stop, nnz_sel in self._runs:
+            seg = BatchSegments(X, self._perm[first * B:stop * B], B, nnz_sel, self._drop,
+                                self._vals_drop)
+            vals = X.data if self._drop is None else self._vals_drop
+            for b in range(first, stop):
+                rows = self._perm[b * B:(b + 1) * B]
+                y = self._y_epoch[b * B:(b + 1) * B]
+                h = self._hidden(X, vals, rows, B)
+                opt.zero_grad()
+                h.requires_grad_(True)
+                with torch.enable_grad():
+                    O = self._proj.matmul(h, self.W2, self.b2)
+                nll, dO, _ = nll_forward_backward(O.detach(), y)
+                O.backward(dO)
+                pen = self._penalty()  # of W1 before its update, as f_train reports it
+                total += nll if pen is None else nll + pen
+                hd = h.detach()
+                g = torch.addcmul(h.grad, h.grad, hd * hd, value=-1.0)  # dh (1 - h^2)
+                opt.prepare()
+                w1_step(self.W1, self.m1, self.v1, g, seg, b - first, l1, l2, opt.a_t, opt.beta1,
+                        opt.beta2, opt.eps)
+                self.b1.grad = gs.colsum(g)
+                opt.apply()
+        return total / self._n_batches
+
+    def _train_epoch(self, order=None) -> torch.Tensor:
+        if order is None:  # lang2loc.py:398-400 (mlp.iterate_minibatch_indices' draw), numpy's
+            order = np.arange(self.Xd.n_rows)  # global stream
+            np.random.shuffle(order)
+        self._prepare_epoch(order)
+        return self._run_batches()
+
+    @torch.no_grad()
+    def fit(self, X_train, Y_train, X_dev, Y_dev, *ignored, epoch_orders=None):
+        """lang2loc.py:408-455. The reference's six further arguments (X_test, Y_test, U_train,
+        U_dev, U_test, userLocation) are accepted and ignored, as fit ignores them there.
+        epoch_orders (tests, measurement): one permutation of the training rows per epoch
+        instead of the np.random.shuffle draws."""
+        for X in (X_train, X_dev):
+            if not (isinstance(X, gs.DeviceCSR) or sps.issparse(X)):
+                raise ValueError("Input for this layer must be sparse")
+        in_size = X_train.shape[1]
+        if self.input_size is not None and int(self.input_size) != in_size:
+            raise ValueError(f"X_train has {in_size} columns, input_size says {self.input_size}")
+        if X_dev.shape[1] != in_size:
+            raise ValueError("X_train and X_dev differ in width")
+        n_batches(X_train.shape[0], self.batch_size)  # n < B raises
+        if X_dev.shape[0] < self.batch_size:
+            raise ValueError(f"{X_dev.shape[0]} dev rows are fewer than one batch of "
+                             f"{self.batch_size}: the dev loss is a mean over whole batches")
+        self._y_train = self._coords(Y_train, X_train.shape[0], "Y_train")
+        y_dev = self._coords(Y_dev, X_dev.shape[0], "Y_dev")
+        self.Xd = X_train if isinstance(X_train, gs.DeviceCSR) else \
+            gs.DeviceCSR.from_scipy(X_train, self.device)
+        self.Xdev = X_dev if isinstance(X_dev, gs.DeviceCSR) else \
+            gs.DeviceCSR.from_scipy(X_dev, self.device)
+        self._indptr_host = (np.asarray(X_train.indptr) if sps.issparse(X_train) and
+                             X_train.format == "csr" else self.Xd.indptr.cpu().numpy()
+                             ).astype(np.int64)
+        self._build(in_size)
+        # X's values behind the mask: every batch's rows are rewritten by its segmentation call
+        self._vals_drop = torch.zeros_like(self.Xd.data) if self._drop is not None else None
+        log.info("training with %d n_epochs and %d batch_size", self.n_epochs, self.batch_size)
+        self.history = []
+        best_params, best_val_loss, n_down = None, float("inf"), 0
+        for n in range(self.n_epochs):
+            order = None if epoch_orders is None else epoch_orders[n]
+            l_train = self._train_epoch(order)
+            l_val = self._evaluate(self.Xdev, y_dev)
+            l_train, l_val = float(l_train), float(l_val)
+            stop = False
+            if l_val < best_val_loss:
+                best_val_loss, n_down = l_val, 0
+                best_params = [p.detach().clone() for p in self.params]
+            else:
+                n_down += 1
+                stop = n_down > self.early_stopping_max_down
+            self.history.append({"epoch": n, "train_loss": l_train, "val_loss": l_val})
+            if stop:
+                log.info("validation results went down. early stopping ...")
+                break
+            log.info("iter %d, train loss %f, dev loss %f, best dev loss %f, num_down %d", n,
+                     l_train, l_val, best_val_loss, n_down)
+        if best_params is not None:  # None: no epoch gave a finite improvement; keep the last
+            for p, b in zip(self.params, best_params):
+                p.copy_(b)
+        self.best_val_loss = best_val_loss
+        return self
+
+    # -- reference API ------------------------------------------------------------------
+    def predict_params(self, X):
+        """f_predict (lang2loc.py:329): mus [n, 2, C], sigmas [n, 2, C], corxy [n, C],
+        pis [n, C] as NumPy arrays."""
+        O = self._output(self._input(X))
+        return tuple(t.cpu().numpy() for t in unpack_params(O, self.n_bigaus_comp))
+
+    def predict(self, X, prediction_method: str = "mixture"):
+        """lang2loc.py:460-463: the selected means, n x 2 (lat, lon), for every row of X."""
+        O = self._output(self._input(X))
+        return mdn_predict(O, self.n_bigaus_comp, prediction_method).cpu().numpy()
+
+    def get_params(self):
+        return [p.detach().cpu().numpy() for p in self.params]
+
+    def set_params(self, params):
+        """lang2loc.py:394-395 (on a fitted model)."""
+        with torch.no_grad():
+            for p, v in zip(self.params, params):
+                p.copy_(_as_tensor(v, tuple(p.shape), self.device))
+        self._proj.invalidate()

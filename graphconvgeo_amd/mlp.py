@@ -97,12 +97,44 @@ def input_convolution(H, X, device="cuda") -> gs.DeviceCSR:
     return gs.spgemm(gs.DeviceCSR.from_scipy(Hc, Xd.device), Xd)
 
 
+def plan_epoch(order, indptr_host: np.ndarray, batch: int):
+    """Host half of an epoch's segmentation: (perm, runs, n_batches). perm is the order cut to
+    whole batches (int64, range-checked); runs are (first batch, stop batch, selected entries)
+    triples, greedy runs of whole batches under SEGMENT_CHUNK_ENTRIES, one segmentation call
+    each. The sizes come from the host's copy of indptr: no synchronisation."""
+    n = indptr_host.size - 1
+    order = np.asarray(order)
+    if order.ndim != 1 or order.size != n:
+        raise ValueError(f"an epoch's order must list the {n} training rows")
+    nb = n_batches(n, batch)
+    perm = np.ascontiguousarray(order[:nb * batch], dtype=np.int64)
+    if perm.min() < 0 or perm.max() >= n:
+        raise IndexError("epoch order out of range")
+    lens = indptr_host[perm + 1] - indptr_host[perm]
+    per_batch = lens.reshape(nb, batch).sum(axis=1)
+    runs, start, acc = [], 0, 0
+    for b in range(nb):
+        if b > start and acc + int(per_batch[b]) > SEGMENT_CHUNK_ENTRIES:
+            runs.append((start, b, acc))
+            start, acc = b, 0
+        acc += int(per_batch[b])
+    runs.append((start, nb, acc))
+    return perm, runs, nb
+
+
 class BatchSegments:
     """The column grouping of a run of consecutive batches (gcg_minibatch_segment): batch b of
     the run owns segments batch_seg_ptr[b] .. batch_seg_ptr[b+1]; segment s has column
-    seg_col[s] and entries seg_ptr[s] .. seg_ptr[s+1] of (ent_pos, ent_val)."""
+    seg_col[s] and entries seg_ptr[s] .. seg_ptr[s+1] of (ent_pos, ent_val).
 
-    def __init__(self, X: gs.DeviceCSR, perm: torch.Tensor, batch: int, nnz_sel: int):
+    drop (a dropout.DropoutSpec) with vals_drop (float32[X.nnz]): input dropout on X at
+    segmentation (gcg_minibatch_segment_dropout). Batch b of the run is masked under step
+    s0 + b, s0 the stream's current step (`first_step`); ent_val holds the masked values and
+    vals_drop receives them at the selected rows' CSR slots, for the forward. The stream is
+    advanced by the run's number of batches afterwards."""
+
+    def __init__(self, X: gs.DeviceCSR, perm: torch.Tensor, batch: int, nnz_sel: int,
+                 drop=None, vals_drop: torch.Tensor = None):
         gs._require_cuda(perm, "perm")
         if perm.dtype != torch.int32 or perm.dim() != 1 or not perm.is_contiguous():
             raise TypeError("perm must be a contiguous 1-D int32 tensor")
@@ -121,10 +153,27 @@ class BatchSegments:
             self.ent_pos = torch.empty(max(nnz_sel, 1), dtype=torch.int32, device=dev)
             self.ent_val = torch.empty(max(nnz_sel, 1), dtype=torch.float32, device=dev)
             ws = torch.empty((nb.value + 7) // 8, dtype=torch.int64, device=dev)
-            call("gcg_minibatch_segment", X.n_rows, X.n_cols, _ptr(X.indptr), _ptr(X.indices),
-                 _ptr(X.data), _ptr(perm), n_sel, batch, nnz_sel, _ptr(self.batch_seg_ptr),
-                 _ptr(self.seg_col), _ptr(self.seg_ptr), _ptr(self.ent_pos), _ptr(self.ent_val),
-                 _ptr(ws), ws.numel() * 8, _stream_handle(dev))
+            if drop is None:
+                call("gcg_minibatch_segment", X.n_rows, X.n_cols, _ptr(X.indptr),
+                     _ptr(X.indices), _ptr(X.data), _ptr(perm), n_sel, batch, nnz_sel,
+                     _ptr(self.batch_seg_ptr), _ptr(self.seg_col), _ptr(self.seg_ptr),
+                     _ptr(self.ent_pos), _ptr(self.ent_val), _ptr(ws), ws.numel() * 8,
+                     _stream_handle(dev))
+                return
+            gs._require_cuda(vals_drop, "vals_drop")
+            if vals_drop.dtype != torch.float32 or vals_drop.numel() != X.nnz or \
+                    not vals_drop.is_contiguous():
+                raise ValueError("vals_drop must be a contiguous float32[nnz] device tensor")
+            stream = drop.stream
+            if stream.step < 0:  # a fresh stream: step 0 is what its device scalar holds
+                stream.set_step(0)
+            self.first_step = stream.step
+            call("gcg_minibatch_segment_dropout", X.n_rows, X.n_cols, _ptr(X.indptr),
+                 _ptr(X.indices), _ptr(X.data), _ptr(perm), n_sel, batch, nnz_sel,
+                 _ptr(self.batch_seg_ptr), _ptr(self.seg_col), _ptr(self.seg_ptr),
+                 _ptr(self.ent_pos), _ptr(self.ent_val), _ptr(vals_drop), _ptr(ws),
+                 ws.numel() * 8, *drop.abi(), _stream_handle(dev))
+            stream.set_step(self.first_step + self.n_batches)
 
 
 def w1_step(W: torch.Tensor, m: torch.Tensor, v: torch.Tensor, G: torch.Tensor,
@@ -283,24 +332,7 @@ class MLP:
     def _prepare_epoch(self, order) -> None:
         """Host half of an epoch: the order cut into whole batches, checked once, uploaded;
         its labels gathered once; the runs of batches each segmentation call takes."""
-        B, n = self.batch_size, self.Xd.n_rows
-        order = np.asarray(order)
-        if order.ndim != 1 or order.size != n:
-            raise ValueError(f"an epoch's order must list the {n} training rows")
-        nb = n_batches(n, B)
-        perm = np.ascontiguousarray(order[:nb * B], dtype=np.int64)
-        if perm.min() < 0 or perm.max() >= n:
-            raise IndexError("epoch order out of range")
-        lens = self._indptr_host[perm + 1] - self._indptr_host[perm]
-        per_batch = lens.reshape(nb, B).sum(axis=1)
-        runs, start, acc = [], 0, 0
-        for b in range(nb):  # greedy runs of whole batches under SEGMENT_CHUNK_ENTRIES
-            if b > start and acc + int(per_batch[b]) > SEGMENT_CHUNK_ENTRIES:
-                runs.append((start, b, acc))
-                start, acc = b, 0
-            acc += int(per_batch[b])
-        runs.append((start, nb, acc))
-        self._runs = runs
+        perm, self._runs, nb = plan_epoch(order, self._indptr_host, self.batch_size)
         self._perm_host = perm
         self._perm = torch.from_numpy(perm.astype(np.int32)).to(self.device)
         self._y_epoch = self._y_train.index_select(0, self._perm.to(torch.int64))

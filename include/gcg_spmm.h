@@ -414,6 +414,88 @@ gcg_status gcg_minibatch_w1_step_f32(int64_t F, int64_t K, float* W, float* m, f
                                      gcg_stream_t stream);
 
 /*
+ * gcg_minibatch_segment_dropout: gcg_minibatch_segment with input dropout on X (the reference's
+ * SparseInputDropoutLayer in front of a mini-batch trainer, lang2loc.py:280-281), the dropout
+ * parameters of gcg_csr_dropout_f32 appended. Every selected entry is masked with the keep rule
+ * above: logical row = the row's id in X, logical column = its column, step = *step_dev + the
+ * batch's index in the call (so one call draws an independent mask per batch, and the host
+ * advances its step counter by n_batches afterwards). The masked value -- keep ? fl32(v * scale)
+ * : +0.0 -- is written twice: as the entry's ent_val (the W1 step sees the masked batch) and
+ * into vals_drop (float32[nnz of X]) at the entry's own CSR slot, so the forward of batch b is
+ * gcg_spmm_csr_f32_gate(indptr, indices, vals_drop, out_rows = the batch's rows). Each row of an
+ * epoch's order is in at most one batch, so one vals_drop serves every batch of the call; slots
+ * of rows outside perm are not written. Dropped entries stay explicit zeros; the segment
+ * structure (batch_seg_ptr, seg_col, seg_ptr, ent_pos) is bitwise gcg_minibatch_segment's.
+ * Sizes and workspace as gcg_minibatch_segment (gcg_minibatch_segment_sizes).
+ */
+gcg_status gcg_minibatch_segment_dropout(int64_t n_rows, int64_t n_cols, const int32_t* indptr,
+                                         const int32_t* indices, const float* vals,
+                                         const int32_t* perm, int64_t n_sel, int64_t batch,
+                                         int64_t nnz_sel, int32_t* batch_seg_ptr, int32_t* seg_col,
+                                         int32_t* seg_ptr, int32_t* ent_pos, float* ent_val,
+                                         float* vals_drop, void* workspace, size_t workspace_bytes,
+                                         uint32_t threshold, float scale, uint64_t seed,
+                                         const int32_t* step_dev, uint32_t stream_id,
+                                         gcg_stream_t stream);
+
+/*
+ * The mixture-density location head (reference lang2loc.py:143-244): a network output row of
+ * 6 * C float32 values read as a mixture of C bivariate Gaussians over (lat, lon). The layout is
+ * the reference's output.reshape(-1, 6, C): row r of O (B x 6C, row stride ldo >= 6C) holds six
+ * planes of C columns,
+ *     plane 0, 1   means         mu    = (90, 180) * tanh(.)
+ *     plane 2, 3   sigmas        sigma = 10 * softplus(.)
+ *     plane 4      correlation   rho   = softsign(.) = t / (1 + |t|)
+ *     plane 5      mixture logits   pi = softmax(.) over the C components
+ * with 1 <= C <= 1024. softplus is evaluated as max(x, 0) + log1p(exp(-|x|)), log pi as
+ * log-softmax, and 1 - rho^2 from the raw value as (1 + 2|t|) / (1 + |t|)^2: the same functions
+ * as the reference's expressions wherever those are finite, without their overflow (softplus,
+ * log(softmax)) and cancellation (1 - rho^2 as |rho| -> 1). Arithmetic is float32 with the
+ * device library's expf / logf / log1pf / tanhf (no fast intrinsics), with one exception in
+ * gcg_mdn_nll_f32: the difference y - mu is formed in double (tanh included) and rounded once,
+ * because mu rounded to float32 (|mu| up to 180) is off by up to 8e-6 and y - mu amplifies that
+ * as a mean closes in on its target. The calls validate on the host, allocate nothing, and
+ * return GCG_OK without a launch when B == 0.
+ *
+ * gcg_mdn_nll_f32: the negative log-likelihood of Y (B x 2 float32, contiguous: lat, lon) and
+ * its gradient (lang2loc.py:166-196). With d = y - mu, u_i = d_i / sigma_i,
+ *     z_c = u1^2 + u2^2 - 2 rho u1 u2
+ *     e_c = -z_c / (2 (1 - rho^2)) - log(2 pi) - log(sigma1 sigma2) - log(1 - rho^2) / 2 + log pi_c
+ *     loss_r = -logsumexp_c(e_c)
+ * One launch computes every row's loss and gradient: one wave per row, lanes striding over the
+ * components, the wave reductions by __shfl in a fixed order. loss_rows (nullable) receives
+ * loss_r; *loss (device scalar) the mean, reduced by a second one-workgroup launch in a fixed
+ * order with no atomics -- thread t of 256 adds the rows t, t + 256, ... in order, the 256
+ * partials are added by a halving tree (p[t] += p[t + h], h = 128 .. 1), the sum is divided by
+ * B -- so it is reproducible bit for bit. dO (B x 6C, row stride ldd >= 6C; NULL: no gradient,
+ * for validation) receives s / B * d loss_r / d O[r][.], s = *scale_dev (the upstream gradient,
+ * a device scalar) or 1 when NULL -- the convention of gcg_l1l2_grad_f32. workspace: B floats,
+ * needed only when loss_rows is NULL (the row losses the mean is taken of live there).
+ *
+ * gcg_mdn_unpack_f32: the four arrays of the reference's f_predict, contiguous float32:
+ * mus [B, 2, C], sigmas [B, 2, C], corxy [B, C], pis [B, C] -- computed with the device
+ * functions the other two calls use, so gcg_mdn_predict_f32's latlon is bitwise a mus entry.
+ *
+ * gcg_mdn_predict_f32: the reference's pred (lang2loc.py:198-244). method 0 ("mixture"): every
+ * component mean mu_c of a row is a candidate, its score the mixture density there,
+ *     sum_k pi_k / (2 pi sigma1_k sigma2_k sqrt(1 - rho_k^2)) * exp(-z_ck / (2 (1 - rho_k^2)))
+ * summed over k ascending in float32 (non-log form; the candidate's own component contributes
+ * exp(0), so the score is positive unless its weight underflows); method 1 ("pi"): the score is
+ * the component's logit. idx[r] (int32, nullable) is the first maximiser (numpy.argmax: the
+ * lower index on a tie), latlon[r] = (mu_lat, mu_lon) of it (float32 B x 2). One workgroup per
+ * row, the row's six transformed planes staged once in LDS (24 C bytes); C^2 evaluations per row.
+ */
+gcg_status gcg_mdn_nll_f32(int64_t B, int64_t C, const float* O, int64_t ldo, const float* Y,
+                           const float* scale_dev /*nullable*/, float* dO /*nullable*/,
+                           int64_t ldd, float* loss_rows /*nullable*/, float* loss,
+                           void* workspace /*nullable*/, size_t workspace_bytes,
+                           gcg_stream_t stream);
+gcg_status gcg_mdn_unpack_f32(int64_t B, int64_t C, const float* O, int64_t ldo, float* mus,
+                              float* sigmas, float* corxy, float* pis, gcg_stream_t stream);
+gcg_status gcg_mdn_predict_f32(int64_t B, int64_t C, const float* O, int64_t ldo, int method,
+                               int32_t* idx /*nullable*/, float* latlon, gcg_stream_t stream);
+
+/*
  * CSR transpose on the device (CSR(X^T) for the X^T . dZ1 gradient of
  * mlpconv.py:71). Output is sorted by (row, col) with stable order for equal
  * entries. out_indptr int32[n_cols+1], out_indices int32[nnz], out_vals f32[nnz].
