@@ -33,9 +33,10 @@ _os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "8")
 
 __all__ = ["sparse", "ops", "layers", "dense", "distributed", "dist_train", "graph", "mentions",
            "mlpconv", "mlp", "geo", "mdn", "synth", "MLP", "input_convolution", "NNModel_lang2loc",
-           "DeviceCSR"]
+           "NNModel_lang2locshared", "DeviceCSR"]
 
-_LAZY = {"MLP": "mlp", "input_convolution": "mlp", "NNModel_lang2loc": "mdn", "DeviceCSR": "sparse"}
+_LAZY = {"MLP": "mlp", "input_convolution": "mlp", "NNModel_lang2loc": "mdn",
+         "NNModel_lang2locshared": "mdn", "DeviceCSR": "sparse"}
 
 
 def __getattr__(name):

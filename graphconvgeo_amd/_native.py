@@ -84,6 +84,12 @@ SIGNATURES = {
                                   _p]),
     "gcg_mdn_unpack_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _p, _p, _p, _p]),
     "gcg_mdn_predict_f32": (C.c_int, [_i64, _i64, _p, _i64, C.c_int, _p, _p, _p]),
+    # the shared-component model (lang2loc_mdnshared.py)
+    "gcg_mdn_shared_nll_f32_workspace_bytes": (C.c_int, [_i64, _i64, _psz]),
+    "gcg_mdn_shared_nll_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p,
+                                         _p, _p, _p, C.c_size_t, _p]),
+    "gcg_mdn_shared_density_f32": (C.c_int, [_i64, _p, _p, _p, _p, _p]),
+    "gcg_mdn_shared_predict_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _p, C.c_int, _p, _p, _p]),
     "gcg_csr_validate": (C.c_int, [_i64, _i64, _i64, _p, _p, _p, _p]),
     "gcg_index_csr": (C.c_int, [_i64, _p, _i64, _p, _p, _p, C.c_size_t, _psz, _p]),
     "gcg_scatter_add_rows_f32": (C.c_int, [_i64, _p, _p, _p, _i64, _i64, _p, _i64, _p]),

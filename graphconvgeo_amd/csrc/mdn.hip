@@ -329,6 +329,314 @@ unsigned row_blocks(int64_t B) {
     else LAUNCH(16);                     \
   } while (0)
 
+// ---- the shared-component model (lang2loc_mdnshared.py:306-327, 379-414, 482-487) -----------
+// One set of C Gaussians for the whole model: mus [C, 2] raw, sigmas = softplus(raw [C, 2]),
+// rho = softsign(raw [C]); the network only gives the mixture logits L [B, C].
+
+constexpr int kSharedPlanes = 5;     // s1, s2, rho, q, k of every component, in double
+constexpr int kSharedRowsMin = 4;    // rows per workgroup: one per wave ...
+constexpr int kSharedMaxGroups = 512;  // ... until the grid would pass two workgroups per CU
+
+// Rows per workgroup: a multiple of the waves, a function of B alone.
+int64_t shared_rows_per_group(int64_t B) {
+  const int64_t per = kSharedRowsMin * kSharedMaxGroups;
+  return kSharedRowsMin * std::max<int64_t>(1, (B + per - 1) / per);
+}
+int64_t shared_groups(int64_t B) {
+  const int64_t R = shared_rows_per_group(B);
+  return (B + R - 1) / R;
+}
+
+// What depends on the component alone, once per call, in double: P [5, C] = s1, s2, rho, q and
+//   k = -log(2 pi) - (log s1 + log s2) - 0.5 log q, the row-independent part of e.
+// Double because e is: two components that compete for a row have |e| of 30 .. 1e4 there, and
+// their responsibilities hang on the difference -- float32 transforms and a float32 e leave
+// ulp(|e|) in it.
+__global__ __launch_bounds__(kBlock) void mdn_shared_prep_kernel(
+    int C, const float* __restrict__ sig, const float* __restrict__ cor, double* __restrict__ P) {
+  const int c = blockIdx.x * kBlock + threadIdx.x;
+  if (c >= C) return;
+  const double r1 = sig[2 * c], r2 = sig[2 * c + 1], a = fabs(static_cast<double>(cor[c]));
+  const double s1 = fmax(r1, 0.0) + log1p(exp(-fabs(r1)));
+  const double s2 = fmax(r2, 0.0) + log1p(exp(-fabs(r2)));
+  const double inv1 = 1.0 / (1.0 + a);
+  const double q = (1.0 + 2.0 * a) * (inv1 * inv1);
+  P[c] = s1;
+  P[C + c] = s2;
+  P[2 * C + c] = cor[c] * inv1;
+  P[3 * C + c] = q;
+  P[4 * C + c] = (-1.8378770664093453 - (log(s1) + log(s2))) - 0.5 * log(q);
+}
+
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+  return v;
+}
+
+// Workgroup g walks the rows [g R, (g + 1) R), wave w of it the rows g R + w (R / 4) ... in
+// order, one row at a time with the lanes across the components as in mdn_nll_kernel: loss_rows
+// and dL are per-row work. e is formed in double from the float32 difference y - mu and the
+// double constants, its maximum M over the row taken in double, and x = e - M rounded to
+// float32 (evaluated twice rather than kept: 16 doubles per lane at C = 1024); everything after
+// -- exp, the sums, the gradient terms -- is float32. Each lane keeps the five sums of its
+// components over its wave's rows in registers (row order); the waves add theirs into LDS in
+// wave order (((w0 + w1) + w2) + w3) and the workgroup writes one [5, C] partial. The factors
+// that depend on the component alone are left to mdn_shared_finish_kernel.
+template <int N>
+__global__ __launch_bounds__(kBlock) void mdn_shared_nll_kernel(
+    int64_t B, int C, int64_t R, const float* __restrict__ L, int64_t ldl,
+    const float* __restrict__ Y, const float* __restrict__ mus, const double* __restrict__ P,
+    const float* __restrict__ scale_dev, float* __restrict__ dL, int64_t lddl,
+    float* __restrict__ partials, float* __restrict__ loss_rows) {
+  extern __shared__ float lds[];  // [5, C]
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  const int64_t per_wave = R / kWavesPerBlock;
+  const int64_t r0 = static_cast<int64_t>(blockIdx.x) * R + wave * per_wave;
+  const int64_t r1 = std::min<int64_t>(r0 + per_wave, B);
+  const bool want_grad = dL != nullptr || partials != nullptr;
+  const float up = (scale_dev != nullptr ? *scale_dev : 1.0f) / static_cast<float>(B);
+
+  float acc[5][N];
+#pragma unroll
+  for (int j = 0; j < 5; ++j)
+#pragma unroll
+    for (int i = 0; i < N; ++i) acc[j][i] = 0.0f;
+
+  for (int64_t r = r0; r < r1; ++r) {
+    const float* l = L + r * ldl;
+    const float y1 = Y[2 * r], y2 = Y[2 * r + 1];
+    float lg[N], x[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const int c = lane + i * kWave;
+      lg[i] = c < C ? l[c] : -INFINITY;
+    }
+    const Lse lp = wave_lse<N>(lg);
+    const double log_sum_pi = log(static_cast<double>(lp.sum));
+    // e of the lane's i-th component, -inf past C
+    auto e_of = [&](int i) -> double {
+      const int c = lane + i * kWave;
+      if (c >= C) return -INFINITY;
+      const double rho = P[2 * C + c];
+      const double u1 = static_cast<double>(y1 - mus[2 * c]) / P[c];
+      const double u2 = static_cast<double>(y2 - mus[2 * c + 1]) / P[C + c];
+      const double z = (u1 * u1 + u2 * u2) - 2.0 * rho * (u1 * u2);
+      return ((-0.5 * z) / P[3 * C + c] + P[4 * C + c]) +
+             (static_cast<double>(lg[i] - lp.max) - log_sum_pi);
+    };
+    double M = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < N; ++i) M = fmax(M, e_of(i));
+    M = wave_max(M);
+    float s = 0.0f;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      x[i] = static_cast<float>(e_of(i) - M);
+      s = s + expf(x[i]);
+    }
+    const float sum_e = wave_sum(s);
+    if (lane == 0 && loss_rows != nullptr)
+      loss_rows[r] = static_cast<float>(-(M + static_cast<double>(logf(sum_e))));
+    if (!want_grad) continue;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const int c = lane + i * kWave;
+      if (c < C) {
+        const float w = expf(x[i]) / sum_e;  // the component's responsibility
+        if (dL != nullptr) dL[r * lddl + c] = (expf(lg[i] - lp.max) / lp.sum - w) * up;
+        if (partials != nullptr) {
+          const float s1 = static_cast<float>(P[c]), s2 = static_cast<float>(P[C + c]);
+          const float rho = static_cast<float>(P[2 * C + c]), q = static_cast<float>(P[3 * C + c]);
+          const float u1 = (y1 - mus[2 * c]) / s1, u2 = (y2 - mus[2 * c + 1]) / s2;
+          const float z = (u1 * u1 + u2 * u2) - 2.0f * rho * (u1 * u2);
+          const float a1 = (u1 - rho * u2) / q, a2 = (u2 - rho * u1) / q;
+          acc[0][i] = acc[0][i] + w * (a1 / s1);
+          acc[1][i] = acc[1][i] + w * (a2 / s2);
+          acc[2][i] = acc[2][i] + w * ((u1 * a1 - 1.0f) / s1);
+          acc[3][i] = acc[3][i] + w * ((u2 * a2 - 1.0f) / s2);
+          acc[4][i] = acc[4][i] + w * ((u1 * u2 + rho * (1.0f - z / q)) / q);
+        }
+      }
+    }
+  }
+  if (partials == nullptr) return;  // uniform over the workgroup
+
+  for (int w = 0; w < kWavesPerBlock; ++w) {
+    if (wave == w) {
+#pragma unroll
+      for (int j = 0; j < 5; ++j)
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+          const int c = lane + i * kWave;
+          if (c < C) lds[j * C + c] = w == 0 ? acc[j][i] : lds[j * C + c] + acc[j][i];
+        }
+    }
+    __syncthreads();
+  }
+  float* out = partials + static_cast<int64_t>(blockIdx.x) * 5 * C;
+  for (int t = threadIdx.x; t < 5 * C; t += kBlock) out[t] = lds[t];
+}
+
+// dparams[j][c] = factor_j(c) * (partial of workgroup 0 + 1 + ... in order): thread per (j, c).
+//   d mus: -s/B; d sigmas_raw: -s/B * sigmoid(raw); d corxy_raw: -s/B / (1 + |raw|)^2
+__global__ __launch_bounds__(kBlock) void mdn_shared_finish_kernel(
+    int64_t B, int C, int groups, const float* __restrict__ partials,
+    const float* __restrict__ sig, const float* __restrict__ cor,
+    const float* __restrict__ scale_dev, float* __restrict__ dparams) {
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= 5 * C) return;
+  float s = 0.0f;
+  for (int g = 0; g < groups; ++g) s = s + partials[static_cast<int64_t>(g) * 5 * C + t];
+  const int j = t / C, c = t - j * C;
+  const float up = (scale_dev != nullptr ? *scale_dev : 1.0f) / static_cast<float>(B);
+  float f = -up;
+  if (j == 2 || j == 3) f = f * sigmoid(sig[2 * c + (j - 2)]);
+  if (j == 4) {
+    const Corr k = corr_of(cor[c]);
+    f = f * (k.inv1 * k.inv1);
+  }
+  dparams[t] = f * s;
+}
+
+// Dt[j C + i]: the density of component j at the mean of component i, in mdn_predict_kernel's
+// factoring. Workgroup j, threads over the candidates i (consecutive in memory).
+__global__ __launch_bounds__(kBlock) void mdn_shared_density_kernel(
+    int C, const float* __restrict__ mus, const float* __restrict__ sig,
+    const float* __restrict__ cor, float* __restrict__ Dt) {
+  const int j = blockIdx.x;
+  const float s1 = softplus(sig[2 * j]), s2 = softplus(sig[2 * j + 1]);
+  const Corr k = corr_of(cor[j]);
+  const float qi = 1.0f / k.q;
+  const float sh = sqrtf(0.5f * qi);
+  const float a1 = sh / s1, a2 = sh / s2;
+  const float wgt = kInv2Pi * ((1.0f / s1) * (1.0f / s2)) * sqrtf(qi);
+  const float m1 = mus[2 * j], m2 = mus[2 * j + 1];
+  for (int i = threadIdx.x; i < C; i += kBlock) {
+    const float v1 = (mus[2 * i] - m1) * a1, v2 = (mus[2 * i + 1] - m2) * a2;
+    const float z = (v1 * v1 + v2 * v2) - 2.0f * k.rho * (v1 * v2);
+    Dt[static_cast<int64_t>(j) * C + i] = wgt * expf(-z);
+  }
+}
+
+constexpr int kPredTile = 4;  // rows per workgroup of the shared prediction
+
+// A workgroup takes kPredTile rows: wave w softmaxes row w of the tile into LDS
+// (lanes striding over the components, as the NLL does), then thread t scores the candidates
+// t, t + 256, ... (NC of them) of every row of the tile at once: score[row][i] = sum over j
+// ascending of pi[row][j] * Dt[j][i], each Dt element read once per tile and pi[row][j] an LDS
+// broadcast. A row's numbers do not depend on the tile it falls in. method 1 scores by the logit.
+template <int NC>
+__global__ __launch_bounds__(kBlock) void mdn_shared_predict_kernel(
+    int64_t B, int C, const float* __restrict__ L, int64_t ldl, const float* __restrict__ Dt,
+    const float* __restrict__ mus, int method, int32_t* __restrict__ idx,
+    float* __restrict__ latlon) {
+  extern __shared__ float pis[];  // [kPredTile, C]
+  __shared__ float best_s[kPredTile][kWavesPerBlock];
+  __shared__ int best_i[kPredTile][kWavesPerBlock];
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+  const int64_t r0 = static_cast<int64_t>(blockIdx.x) * kPredTile;
+  const int rows = static_cast<int>(std::min<int64_t>(kPredTile, B - r0));
+
+  for (int t = wave; t < kPredTile; t += kWavesPerBlock) {
+    float* p = pis + t * C;
+    if (t >= rows) {  // a short tile: its spare rows score nothing and are not written
+      for (int c = lane; c < C; c += kWave) p[c] = 0.0f;
+      continue;
+    }
+    const float* l = L + (r0 + t) * ldl;
+    if (method != 0) {
+      for (int c = lane; c < C; c += kWave) p[c] = l[c];
+      continue;
+    }
+    float m = -INFINITY;
+    for (int c = lane; c < C; c += kWave) m = fmaxf(m, l[c]);
+    m = wave_max(m);
+    float s = 0.0f;
+    for (int c = lane; c < C; c += kWave) s = s + expf(l[c] - m);
+    s = wave_sum(s);
+    for (int c = lane; c < C; c += kWave) p[c] = expf(l[c] - m) / s;
+  }
+  __syncthreads();
+
+  float score[kPredTile][NC];
+  if (method == 0) {
+#pragma unroll
+    for (int t = 0; t < kPredTile; ++t)
+#pragma unroll
+      for (int i = 0; i < NC; ++i) score[t][i] = 0.0f;
+#pragma unroll 8
+    for (int j = 0; j < C; ++j) {
+      float d[NC];
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        const int c = tid + i * kBlock;
+        d[i] = c < C ? Dt[static_cast<int64_t>(j) * C + c] : 0.0f;
+      }
+#pragma unroll
+      for (int t = 0; t < kPredTile; ++t) {
+        const float pj = pis[t * C + j];
+#pragma unroll
+        for (int i = 0; i < NC; ++i) score[t][i] = score[t][i] + pj * d[i];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int t = 0; t < kPredTile; ++t)
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        const int c = tid + i * kBlock;
+        score[t][i] = c < C ? pis[t * C + c] : -INFINITY;
+      }
+  }
+
+#pragma unroll
+  for (int t = 0; t < kPredTile; ++t) {
+    float bs = -INFINITY;
+    int bi = INT32_MAX;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+      const int c = tid + i * kBlock;
+      if (c < C) take_better(bs, bi, score[t][i], c);  // ascending c
+    }
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1)
+      take_better(bs, bi, __shfl_xor(bs, off), __shfl_xor(bi, off));
+    if (lane == 0) {
+      best_s[t][wave] = bs;
+      best_i[t][wave] = bi;
+    }
+  }
+  __syncthreads();
+  if (tid < rows) {
+    float bs = best_s[tid][0];
+    int bi = best_i[tid][0];
+    for (int w = 1; w < kWavesPerBlock; ++w) take_better(bs, bi, best_s[tid][w], best_i[tid][w]);
+    // every score NaN leaves no winner: component 0, in bounds
+    const int win = (bi >= 0 && bi < C) ? bi : 0;
+    const int64_t r = r0 + tid;
+    if (idx != nullptr) idx[r] = win;
+    latlon[2 * r] = mus[2 * win];
+    latlon[2 * r + 1] = mus[2 * win + 1];
+  }
+}
+
+gcg_status check_shared(const char* fn, int64_t B, int64_t C, int64_t ldl) {
+  if (B < 0 || B > INT32_MAX || C < 1 || C > kMaxComp)
+    return fail(GCG_ERR_INVALID_ARG, "%s: bad sizes B=%lld C=%lld (1 <= C <= %d)", fn,
+                static_cast<long long>(B), static_cast<long long>(C), kMaxComp);
+  if (ldl < C)
+    return fail(GCG_ERR_INVALID_ARG, "%s: row stride %lld < C = %lld", fn,
+                static_cast<long long>(ldl), static_cast<long long>(C));
+  return GCG_OK;
+}
+
+// The workspace of gcg_mdn_shared_nll_f32: P [5, C] doubles, the partials [groups, 5, C], B row
+// losses.
+size_t shared_nll_bytes(int64_t B, int64_t C) {
+  return sizeof(float) * static_cast<size_t>((2 * kSharedPlanes + 5 * shared_groups(B)) * C + B);
+}
+
 }  // namespace
 
 extern "C" {
@@ -403,6 +711,110 @@ gcg_status gcg_mdn_predict_f32(int64_t B, int64_t C, const float* O, int64_t ldo
   hipLaunchKernelGGL(mdn_predict_kernel, dim3(grid), dim3(kBlock),
                      sizeof(float) * 6 * static_cast<size_t>(C), static_cast<hipStream_t>(stream),
                      B, static_cast<int>(C), O, ldo, method, idx, latlon);
+  GCG_HIP_CHECK(hipGetLastError());
+  return GCG_OK;
+}
+
+gcg_status gcg_mdn_shared_nll_f32_workspace_bytes(int64_t B, int64_t C, size_t* bytes) {
+  const char* fn = "gcg_mdn_shared_nll_f32_workspace_bytes";
+  if (gcg_status s = check_shared(fn, B, C, C)) return s;
+  if (bytes == nullptr) return fail(GCG_ERR_INVALID_ARG, "%s: NULL bytes", fn);
+  *bytes = shared_nll_bytes(B, C);
+  return GCG_OK;
+}
+
+gcg_status gcg_mdn_shared_nll_f32(int64_t B, int64_t C, const float* L, int64_t ldl,
+                                  const float* Y, const float* mus, const float* sigmas_raw,
+                                  const float* corxy_raw, const float* scale_dev, float* dL,
+                                  int64_t lddl, float* dparams, float* loss_rows, float* loss,
+                                  void* workspace, size_t workspace_bytes, gcg_stream_t stream) {
+  const char* fn = "gcg_mdn_shared_nll_f32";
+  if (gcg_status s = check_shared(fn, B, C, ldl)) return s;
+  if (dL != nullptr && lddl < C)
+    return fail(GCG_ERR_INVALID_ARG, "%s: gradient row stride %lld < C", fn,
+                static_cast<long long>(lddl));
+  if (B == 0) return GCG_OK;
+  if (L == nullptr || Y == nullptr || mus == nullptr || sigmas_raw == nullptr ||
+      corxy_raw == nullptr || loss == nullptr)
+    return fail(GCG_ERR_INVALID_ARG, "%s: NULL operand", fn);
+  if (!aligned(L, 4) || !aligned(Y, 4) || !aligned(mus, 4) || !aligned(sigmas_raw, 4) ||
+      !aligned(corxy_raw, 4) || !aligned(scale_dev, 4) || !aligned(dL, 4) ||
+      !aligned(dparams, 4) || !aligned(loss_rows, 4) || !aligned(loss, 4) ||
+      !aligned(workspace, 8))
+    return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B (workspace: 8-B) aligned", fn);
+  if (workspace == nullptr || workspace_bytes < shared_nll_bytes(B, C))
+    return fail(GCG_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes "
+                "(gcg_mdn_shared_nll_f32_workspace_bytes)", fn, workspace_bytes,
+                shared_nll_bytes(B, C));
+  const int c = static_cast<int>(C);
+  const int64_t R = shared_rows_per_group(B);
+  const int groups = static_cast<int>(shared_groups(B));
+  double* P = static_cast<double*>(workspace);
+  float* base = static_cast<float*>(workspace) + 2 * kSharedPlanes * C;
+  float* partials = dparams != nullptr ? base : nullptr;
+  float* rows = loss_rows != nullptr ? loss_rows : base + 5 * static_cast<int64_t>(groups) * C;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const unsigned cblocks = static_cast<unsigned>((C + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(mdn_shared_prep_kernel, dim3(cblocks), dim3(kBlock), 0, st, c,
+                     sigmas_raw, corxy_raw, P);
+  GCG_HIP_CHECK(hipGetLastError());
+#define GCG_MDN_SHARED_NLL(N)                                                                  \
+  hipLaunchKernelGGL((mdn_shared_nll_kernel<N>), dim3(groups), dim3(kBlock),                   \
+                     sizeof(float) * 5 * static_cast<size_t>(C), st, B, c, R, L, ldl, Y, mus,  \
+                     P, scale_dev, dL, lddl, partials, rows)
+  GCG_MDN_DISPATCH(C, GCG_MDN_SHARED_NLL);
+#undef GCG_MDN_SHARED_NLL
+  GCG_HIP_CHECK(hipGetLastError());
+  if (dparams != nullptr) {
+    hipLaunchKernelGGL(mdn_shared_finish_kernel, dim3((5 * c + kBlock - 1) / kBlock),
+                       dim3(kBlock), 0, st, B, c, groups, partials, sigmas_raw, corxy_raw,
+                       scale_dev, dparams);
+    GCG_HIP_CHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(mdn_mean_kernel, dim3(1), dim3(256), 0, st, B, rows, loss);
+  GCG_HIP_CHECK(hipGetLastError());
+  return GCG_OK;
+}
+
+gcg_status gcg_mdn_shared_density_f32(int64_t C, const float* mus, const float* sigmas_raw,
+                                      const float* corxy_raw, float* Dt, gcg_stream_t stream) {
+  const char* fn = "gcg_mdn_shared_density_f32";
+  if (gcg_status s = check_shared(fn, 0, C, C)) return s;
+  if (mus == nullptr || sigmas_raw == nullptr || corxy_raw == nullptr || Dt == nullptr)
+    return fail(GCG_ERR_INVALID_ARG, "%s: NULL operand", fn);
+  if (!aligned(mus, 4) || !aligned(sigmas_raw, 4) || !aligned(corxy_raw, 4) || !aligned(Dt, 4))
+    return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B aligned", fn);
+  hipLaunchKernelGGL(mdn_shared_density_kernel, dim3(static_cast<unsigned>(C)), dim3(kBlock), 0,
+                     static_cast<hipStream_t>(stream), static_cast<int>(C), mus, sigmas_raw,
+                     corxy_raw, Dt);
+  GCG_HIP_CHECK(hipGetLastError());
+  return GCG_OK;
+}
+
+gcg_status gcg_mdn_shared_predict_f32(int64_t B, int64_t C, const float* L, int64_t ldl,
+                                      const float* Dt, const float* mus, int method,
+                                      int32_t* idx, float* latlon, gcg_stream_t stream) {
+  const char* fn = "gcg_mdn_shared_predict_f32";
+  if (gcg_status s = check_shared(fn, B, C, ldl)) return s;
+  if (method != 0 && method != 1)
+    return fail(GCG_ERR_INVALID_ARG, "%s: method %d is neither 0 (mixture) nor 1 (pi)", fn, method);
+  if (B == 0) return GCG_OK;
+  if (L == nullptr || mus == nullptr || latlon == nullptr || (method == 0 && Dt == nullptr))
+    return fail(GCG_ERR_INVALID_ARG, "%s: NULL operand", fn);
+  if (!aligned(L, 4) || !aligned(Dt, 4) || !aligned(mus, 4) || !aligned(idx, 4) ||
+      !aligned(latlon, 4))
+    return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B aligned", fn);
+  const unsigned grid = static_cast<unsigned>((B + kPredTile - 1) / kPredTile);
+  const size_t lds = sizeof(float) * kPredTile * static_cast<size_t>(C);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int c = static_cast<int>(C);
+#define GCG_MDN_SHARED_PREDICT(NC)                                                             \
+  hipLaunchKernelGGL((mdn_shared_predict_kernel<NC>), dim3(grid), dim3(kBlock), lds, st, B, c, \
+                     L, ldl, Dt, mus, method, idx, latlon)
+  if (C <= kBlock) GCG_MDN_SHARED_PREDICT(1);
+  else if (C <= 2 * kBlock) GCG_MDN_SHARED_PREDICT(2);
+  else GCG_MDN_SHARED_PREDICT(4);
+#undef GCG_MDN_SHARED_PREDICT
   GCG_HIP_CHECK(hipGetLastError());
   return GCG_OK;
 }

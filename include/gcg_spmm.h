@@ -496,6 +496,77 @@ gcg_status gcg_mdn_predict_f32(int64_t B, int64_t C, const float* O, int64_t ldo
                                int32_t* idx /*nullable*/, float* latlon, gcg_stream_t stream);
 
 /*
+ * The shared-component mixture-density model (reference lang2loc_mdnshared.py:306-327, 379-414,
+ * 482-487; lasagne_layers.MDNSharedParams): one set of C bivariate Gaussians for the whole
+ * model, 1 <= C <= 1024, held as float32 parameters
+ *     mus [C, 2]          means (lat, lon), used as they are
+ *     sigmas_raw [C, 2]   sigma = softplus(.)            (no factor 10)
+ *     corxy_raw [C]       rho   = softsign(.) = t / (1 + |t|)
+ * all contiguous; the network gives only the mixture logits L (B x C, row stride ldl >= C),
+ * pi = softmax(L) over the C components. softplus, log pi and q = 1 - rho^2 are evaluated in the
+ * stable forms stated above for the per-row head; the difference d_i = y_i - mus[c][i] is plain
+ * float32 (the mean is a parameter, exact in float32, not a rounded tanh). Arithmetic is float32
+ * as for the per-row head, with one exception in gcg_mdn_shared_nll_f32: e_rc is formed in
+ * double -- s, rho, q and the row-independent part of e once per call from the raw parameters,
+ * u_i = d_i / s_i, z and e per row -- its maximum over the row is taken in double, and e - max
+ * is rounded to float32 once. Two components that compete for a row have |e| of 30 .. 1e4
+ * there and their responsibilities hang on the difference; a float32 e leaves ulp(|e|) in it.
+ * The exponentials, the sums and the gradient terms are float32. The calls validate on the
+ * host, allocate nothing, use no atomics, and return GCG_OK without a launch when B == 0.
+ *
+ * gcg_mdn_shared_nll_f32: with s_i = sigma_i, u_i = d_i / s_i,
+ *     z_rc = u1^2 + u2^2 - 2 rho u1 u2
+ *     e_rc = -0.5 z_rc / q - log(2 pi) - log s1 - log s2 - 0.5 log q + log_softmax(L_r)_c
+ *     loss_r = -logsumexp_c(e_rc),   w_rc = exp(e_rc - max_c) / sum_c   (the responsibility)
+ * loss_rows (nullable) receives loss_r and *loss (device scalar) the mean, in the fixed order of
+ * gcg_mdn_nll_f32. dL (B x C, row stride lddl >= C, nullable) receives s / B * (pi - w),
+ * s = *scale_dev or 1 when NULL. dparams (nullable) receives the gradient of s * mean loss in
+ * five planes of C: d mus lat, d mus lon, d sigmas_raw lat, d sigmas_raw lon, d corxy_raw. With
+ * a_1 = (u1 - rho u2) / q, a_2 = (u2 - rho u1) / q the sums over the rows are
+ *     sum_r w a_i / s_i,   sum_r w (u_i a_i - 1) / s_i,   sum_r w (u1 u2 + rho (1 - z / q)) / q
+ * times -s / B, -s / B * sigmoid(sigmas_raw), -s / B / (1 + |corxy_raw|)^2, the factors applied
+ * once after the sum. The order of every sum is fixed, so the result is reproducible bit for bit:
+ * with R = 4 * max(1, ceil(B / 2048)) rows per workgroup (a function of B alone; at most 512
+ * workgroups), workgroup g takes the rows [g R, (g + 1) R) and its wave w (of 4) the R / 4 rows
+ * from g R + w R / 4, one row at a time with the lanes across the components. A lane adds its
+ * components' terms in row order; the four waves are added as ((w0 + w1) + w2) + w3; a second
+ * launch adds the workgroups' partials in ascending g and applies the factors. loss_rows[r] and
+ * dL[r] depend on row r alone, not on B or the grouping (s / B aside).
+ * workspace: gcg_mdn_shared_nll_f32_workspace_bytes(B, C) bytes, 8-byte aligned, always required
+ * (the components' constants, the workgroups' partials, and the row losses when loss_rows is
+ * NULL).
+ *
+ * gcg_mdn_shared_density_f32: Dt (C x C, contiguous), Dt[j C + i] = the density of component j
+ * at the mean of component i,
+ *     1 / (2 pi s1_j s2_j sqrt(q_j)) * exp(-(v1^2 + v2^2 - 2 rho_j v1 v2)),
+ *     v_i = (mus[i] - mus[j]) * sqrt(0.5 / q_j) / s_j
+ * (gcg_mdn_predict_f32's factoring): C^2 exponentials once per parameter set, not per row.
+ *
+ * gcg_mdn_shared_predict_f32: the reference's pred_sharedparams. method 0 ("mixture"):
+ * score[r][i] = sum_j pi[r][j] * Dt[j C + i], summed over j ascending in float32, with
+ * pi = exp(L - max) / sum (lane l of a wave adds the components l, l + 64, ..., then a butterfly
+ * over the wave); method 1 ("pi"): the score is the logit (Dt may be NULL). idx[r] (int32,
+ * nullable) is the first maximiser (the lower index on a tie; component 0 when every score is
+ * NaN) and latlon[r] (float32 B x 2) = mus[idx[r]], copied bit for bit. A workgroup takes a tile
+ * of 4 rows and reads each Dt element once for the tile; a row's result does not depend on the
+ * tile or the grid.
+ */
+gcg_status gcg_mdn_shared_nll_f32_workspace_bytes(int64_t B, int64_t C, size_t* bytes);
+gcg_status gcg_mdn_shared_nll_f32(int64_t B, int64_t C, const float* L, int64_t ldl,
+                                  const float* Y, const float* mus, const float* sigmas_raw,
+                                  const float* corxy_raw, const float* scale_dev /*nullable*/,
+                                  float* dL /*nullable*/, int64_t lddl,
+                                  float* dparams /*nullable*/, float* loss_rows /*nullable*/,
+                                  float* loss, void* workspace, size_t workspace_bytes,
+                                  gcg_stream_t stream);
+gcg_status gcg_mdn_shared_density_f32(int64_t C, const float* mus, const float* sigmas_raw,
+                                      const float* corxy_raw, float* Dt, gcg_stream_t stream);
+gcg_status gcg_mdn_shared_predict_f32(int64_t B, int64_t C, const float* L, int64_t ldl,
+                                      const float* Dt /*nullable for method 1*/,
+                                      const float* mus, int method, int32_t* idx /*nullable*/,
+                                      float* latlon, gcg_stream_t stream);
+
+/*
  * CSR transpose on the device (CSR(X^T) for the X^T . dZ1 gradient of
  * mlpconv.py:71). Output is sorted by (row, col) with stable order for equal
  * entries. out_indptr int32[n_cols+1], out_indices int32[nnz], out_vals f32[nnz].

@@ -10,6 +10,12 @@ step (one JSON line per measurement; B = 1000 rows, hid = 300, C = 100 / 300 / 9
   step      one NNModel_lang2loc training step (forward over the batch's rows, tanh, output
             GEMM, NLL, backward GEMMs, tanh backward, W1 step) at F = 10,000, 64 nonzeros per
             row, with and without input dropout; host clock per step over an epoch of 20.
+The shared-component model (--only, not in the default set):
+  shared          gcg_mdn_shared_nll_f32 (loss, the logits' and the 5 C parameter gradients, one
+                  call of four launches) against the torch-autograd composition of the formulas.
+  shared_predict  gcg_mdn_shared_predict_f32 ("mixture") against torch.softmax(L) @ Dt and
+                  argmax, the C x C density table given to both; the table's time beside them.
+  shared_step     one NNModel_lang2locshared training step, beside NNModel_lang2loc's.
 Every pair alternates A and B in one process; medians of --steps (>= 20) after --warmup.
 """
 from __future__ import annotations
@@ -155,19 +161,113 @@ def bench_step(dev, C, steps, warmup, F=10_000, nnz=64, n_batches=20):
     return out
 
 
+# -- the shared-component model (lang2loc_mdnshared.py) ----------------------------------------
+def shared_inputs(dev, C, seed):
+    """Logits, targets and the default initialisation's components (sigmas_raw in [10, 20])."""
+    gen = torch.Generator().manual_seed(seed)
+    span = torch.tensor([60.0, 170.0])
+    L = torch.randn(B, C, generator=gen)
+    Y = (torch.rand(B, 2, generator=gen) * 2 - 1) * span
+    mus = (torch.rand(C, 2, generator=gen) * 2 - 1) * span
+    sig = 10 + 10 * torch.rand(C, 2, generator=gen)
+    cor = torch.randn(C, generator=gen)
+    return tuple(t.to(dev) for t in (L, Y, mus, sig, cor))
+
+
+def torch_shared_nll(L, Y, mus, sig, cor):
+    """lang2loc_mdnshared.nll_loss_sharedparams, line by line (log pi as log_softmax)."""
+    sigmas = torch.nn.functional.softplus(sig)
+    corxy = torch.nn.functional.softsign(cor)
+    diff = Y[:, None, :] - mus[None, :, :]
+    sigmainvs = 1.0 / sigmas
+    sigmainvprods = sigmainvs[:, 0] * sigmainvs[:, 1]
+    z = (diff ** 2 / sigmas ** 2).sum(dim=-1) - 2 * corxy * diff[:, :, 0] * diff[:, :, 1] * sigmainvprods
+    inv = 1.0 / (1.0 - corxy ** 2)
+    e = math.log(0.5 / math.pi) + torch.log(sigmainvprods) + torch.log(torch.sqrt(inv)) + \
+        -0.5 * z * inv + torch.log_softmax(L, dim=1)
+    return -torch.logsumexp(e, dim=1).mean()
+
+
+def bench_shared(dev, C, steps, warmup):
+    L, Y, mus, sig, cor = shared_inputs(dev, C, 1)
+
+    def fused():
+        M.shared_nll_forward_backward(L, Y, mus, sig, cor)
+
+    def composed():
+        leaves = [t.detach().requires_grad_(True) for t in (L, mus, sig, cor)]
+        torch_shared_nll(leaves[0], Y, *leaves[1:]).backward()
+
+    d = alternate(fused, composed, steps, warmup, lambda f: device_ms(f, 10))
+    w = alternate(fused, composed, steps, warmup, wall_ms)
+    return {"what": "shared_nll_fwd_bwd", "B": B, "C": C, "fused_device_ms": d[0],
+            "torch_device_ms": d[1], "fused_wall_ms": w[0], "torch_wall_ms": w[1]}
+
+
+def bench_shared_predict(dev, C, steps, warmup):
+    """pis . Dt and the arg-max, the C x C table given to both (it is per parameter set); the
+    table's own time is reported beside them."""
+    L, _, mus, sig, cor = shared_inputs(dev, C, 2)
+    Dt = M.shared_density(mus, sig, cor)
+
+    def fused():
+        return M.shared_predict(L, mus, sig, cor, density=Dt)
+
+    def composed():
+        return mus[(torch.softmax(L, dim=1) @ Dt).argmax(dim=1)]
+
+    same = bool((fused() == composed()).all(dim=1).float().mean() > 0.99)
+    d = alternate(fused, composed, steps, warmup, lambda f: device_ms(f, 10))
+    t, _ = alternate(lambda: M.shared_density(mus, sig, cor), lambda: None, steps, warmup,
+                     lambda f: device_ms(f, 10))
+    return {"what": "shared_predict_mixture", "B": B, "C": C, "fused_device_ms": d[0],
+            "torch_device_ms": d[1], "density_table_device_ms": t, "agree_99pct": same}
+
+
+def bench_shared_step(dev, C, steps, warmup, F=10_000, nnz=64, n_batches=20):
+    """One NNModel_lang2locshared training step beside NNModel_lang2loc's, the same data."""
+    n = n_batches * B
+    X = synthetic_features(n + B, F, nnz_per_row=nnz)
+    rng = np.random.default_rng(3)
+    Y = np.stack([rng.uniform(-60, 60, n + B), rng.uniform(-170, 170, n + B)], axis=1).astype(np.float32)
+    out = {"what": "shared_train_step", "B": B, "C": C, "F": F, "hid": HID, "nnz_per_row": nnz,
+           "steps_per_epoch": n_batches}
+    models = {}
+    for name, cls, drop in (("shared_plain", M.NNModel_lang2locshared, False),
+                            ("shared_dropout", M.NNModel_lang2locshared, True),
+                            ("per_row_plain", M.NNModel_lang2loc, False)):
+        np.random.seed(0)
+        clf = cls(n_epochs=0, batch_size=B, hid_size=HID, ncomp=C, drop_out=drop, device=dev)
+        clf.fit(X[:n], Y[:n], X[n:], Y[n:])
+        models[name] = clf
+    times = {k: [] for k in models}
+    for i in range(warmup + steps):
+        order = rng.permutation(n)
+        for name, clf in models.items():
+            t = wall_ms(lambda: clf._train_epoch(order)) / n_batches
+            if i >= warmup:
+                times[name].append(t)
+    for name in models:
+        out[f"{name}_ms_per_step"] = med(times[name])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--components", type=int, nargs="+", default=[100, 300, 900])
-    ap.add_argument("--only", choices=["nll", "predict", "step"], nargs="+",
+    ap.add_argument("--only", choices=["nll", "predict", "step", "shared", "shared_predict",
+                                       "shared_step"], nargs="+",
                     default=["nll", "predict", "step"])
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     if args.steps < 20:
         ap.error("--steps must be at least 20 (medians of 20)")
     dev = torch.device("cuda:0")
-    benches = {"nll": bench_nll, "predict": bench_predict, "step": bench_step}
+    benches = {"nll": bench_nll, "predict": bench_predict, "step": bench_step,
+               "shared": bench_shared, "shared_predict": bench_shared_predict,
+               "shared_step": bench_shared_step}
     for what in args.only:
         for C in args.components:
             line = json.dumps(benches[what](dev, C, args.steps, args.warmup))
