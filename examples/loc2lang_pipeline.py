@@ -1,0 +1,74 @@
+#!/usr/bin/env python
+"""The location-to-language model on synthetic data, end to end on the GPU:
+
+  k-d-tree regions of the training coordinates (geo.KDTreeClustering)
+  -> the regions' means, deviations and correlations (mdn.cluster_params) as the initial Gaussians
+  -> NNModel_loc2lang.fit on (coordinate, bag of words) pairs
+  -> the word distribution over a coordinate grid -> the most local words (local_words).
+
+Three places, each with words of its own and a few that everybody uses; the local words found
+at the end should be the places' own.
+
+    python examples/loc2lang_pipeline.py [--epochs 40]
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+import scipy.sparse as sps
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from graphconvgeo_amd import geo, loc2lang, mdn  # noqa: E402
+
+PLACES = np.array([[40.7, -74.0], [34.0, -118.2], [29.8, -95.4]])
+OWN, COMMON = 10, 10  # words per place, words of everybody
+
+
+def synthetic(n, rng):
+    place = rng.integers(0, len(PLACES), size=n)
+    X = (PLACES[place] + 0.7 * rng.standard_normal((n, 2))).astype(np.float32)
+    V = OWN * len(PLACES) + COMMON
+    Y = np.zeros((n, V), np.float32)
+    for r in range(n):
+        Y[r, OWN * place[r] + rng.choice(OWN, size=4, replace=False)] = 1
+        Y[r, OWN * len(PLACES) + rng.choice(COMMON, size=4, replace=False)] = 1
+    Y /= Y.sum(axis=1, keepdims=True)  # the l1-normalised bag of words
+    return X, sps.csr_matrix(Y)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
+    ap.add_argument("--epochs", type=int, default=40)
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args()
+    rng = np.random.default_rng(0)
+    np.random.seed(0)
+    (Xtr, Ytr), (Xdev, Ydev), (Xte, Yte) = (synthetic(n, rng) for n in (1200, 300, 300))
+
+    tree = geo.KDTreeClustering(bucket_size=200).fit(Xtr, device=args.device)
+    labels, C = tree.clusters.cpu().numpy(), tree.num_clusters
+    mus, sigmas, corxy = mdn.cluster_params(Xtr, labels, C, raw=True)
+    print(f"{C} regions -> {C} Gaussians")
+
+    clf = loc2lang.NNModel_loc2lang(n_epochs=args.epochs, batch_size=100, hid_size=32,
+                                    n_gaus_comp=C, mus=mus, sigmas=sigmas, corxy=corxy,
+                                    early_stopping_max_down=5, device=args.device)
+    ppl_test, ppl_dev = clf.fit(Xtr, Ytr, Xdev, Ydev, Xte, Yte)
+    first, last = clf.history[0], clf.history[-1]
+    print(f"dev loss {first['val_loss']:.3f} -> {last['val_loss']:.3f} in {len(clf.history)} epochs; "
+          f"perplexity dev {ppl_dev:.2f}, test {ppl_test:.2f}")
+
+    lat, lon = np.meshgrid(np.linspace(27, 43, 17), np.linspace(-121, -71, 26), indexing="ij")
+    grid = np.stack([lat.ravel(), lon.ravel()], axis=1).astype(np.float32)
+    words = loc2lang.local_words(clf.predict(grid), k=12)
+    local = int((words < OWN * len(PLACES)).sum())
+    print("most local words:", words.tolist(), f"({local} of 12 belong to one place)")
+    return 0 if local >= 10 else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -15,9 +15,12 @@ Product modules (all compute runs in libgcg_spmm.so HIP kernels; no CPU fallback
                geo_eval (mean / median km, Acc@161) on the GPU, data.py:399-419
   mdn          the mixture-density location head (lang2loc.py): fused NLL + gradient, the
                "mixture" prediction rule, NNModel_lang2loc (text -> lat/lon) on the GPU
+  loc2lang     the location-to-language model (loc2lang.py): the Gaussian layer, softmax
+               cross-entropy against sparse soft targets, Adamax, NNModel_loc2lang (lat/lon -> words)
   synth        seeded synthetic graphs / features for the BASELINE configs
 
-`MLP`, `input_convolution`, `NNModel_lang2loc` and `DeviceCSR` are imported lazily from the package itself.
+`MLP`, `input_convolution`, `NNModel_lang2loc`, `NNModel_lang2locshared`, `NNModel_loc2lang` and
+`DeviceCSR` are imported lazily from the package itself.
 """
 import os as _os
 
@@ -32,11 +35,11 @@ __version__ = "0.1.0"
 _os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "8")
 
 __all__ = ["sparse", "ops", "layers", "dense", "distributed", "dist_train", "graph", "mentions",
-           "mlpconv", "mlp", "geo", "mdn", "synth", "MLP", "input_convolution", "NNModel_lang2loc",
-           "NNModel_lang2locshared", "DeviceCSR"]
+           "mlpconv", "mlp", "geo", "mdn", "loc2lang", "synth", "MLP", "input_convolution",
+           "NNModel_lang2loc", "NNModel_lang2locshared", "NNModel_loc2lang", "DeviceCSR"]
 
 _LAZY = {"MLP": "mlp", "input_convolution": "mlp", "NNModel_lang2loc": "mdn",
-         "NNModel_lang2locshared": "mdn", "DeviceCSR": "sparse"}
+         "NNModel_lang2locshared": "mdn", "NNModel_loc2lang": "loc2lang", "DeviceCSR": "sparse"}
 
 
 def __getattr__(name):

@@ -90,6 +90,16 @@ SIGNATURES = {
                                          _p, _p, _p, C.c_size_t, _p]),
     "gcg_mdn_shared_density_f32": (C.c_int, [_i64, _p, _p, _p, _p, _p]),
     "gcg_mdn_shared_predict_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _p, C.c_int, _p, _p, _p]),
+    # the location-to-language model (loc2lang.py): the Gaussian layer (csrc/mdn.hip), the
+    # sparse-target cross-entropy (csrc/softmax_csr.hip), Adamax (csrc/csr_ops.hip)
+    "gcg_bigaus_layer_f32": (C.c_int, [_i64, _i64, _p, _p, _p, _p, _p, _i64, _p]),
+    "gcg_bigaus_layer_backward_f32_workspace_bytes": (C.c_int, [_i64, _i64, _psz]),
+    "gcg_bigaus_layer_backward_f32": (C.c_int, [_i64, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _p,
+                                                C.c_size_t, _p]),
+    "gcg_softmax_xent_csr_f32": (C.c_int, [_i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, C.c_float,
+                                           _p, _p, _i64, _p, _p]),
+    "gcg_adamax_step_f32": (C.c_int, [_i64, _p, _p, _p, _p, _p, C.c_float, C.c_float, C.c_float,
+                                      _p]),
     "gcg_csr_validate": (C.c_int, [_i64, _i64, _i64, _p, _p, _p, _p]),
     "gcg_index_csr": (C.c_int, [_i64, _p, _i64, _p, _p, _p, C.c_size_t, _psz, _p]),
     "gcg_scatter_add_rows_f32": (C.c_int, [_i64, _p, _p, _p, _i64, _i64, _p, _i64, _p]),

@@ -190,6 +190,27 @@ __global__ __launch_bounds__(256) void adam_kernel(int64_t n, float* __restrict_
   }
 }
 
+// lasagne.updates.adamax (loc2lang.py:207) for one parameter, in adam_kernel's shape:
+//   m = b1*m + (1-b1)*g;  u = max(b2*u, |g|);  p -= a_t*m / (u + eps)
+// a_t = lr/(1-b1^t) is read on the device.
+__global__ __launch_bounds__(256) void adamax_kernel(int64_t n, float* __restrict__ p,
+                                                     const float* __restrict__ g,
+                                                     float* __restrict__ m, float* __restrict__ u,
+                                                     const float* __restrict__ step_dev, float b1,
+                                                     float b2, float eps) {
+  const float a_t = *step_dev;
+  const float c1 = 1.0f - b1;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float gi = g[i];
+    const float mi = b1 * m[i] + c1 * gi;
+    const float ui = fmaxf(b2 * u[i], fabsf(gi));
+    m[i] = mi;
+    u[i] = ui;
+    p[i] = p[i] - (a_t * mi) / (ui + eps);
+  }
+}
+
 // lasagne.regularization l1 / l2 of one weight (mlpconv.py:235-243): partial sums of |w| and
 // w*w over a fixed grid (kPenBlocks blocks, grid-stride order fixed by the grid), one pair per
 // block; then ONE thread adds the pairs in block order -- deterministic, graph-capturable.
@@ -264,6 +285,19 @@ gcg_status gcg_adam_step_f32(int64_t n, float* p, const float* g, float* m, floa
   if (n == 0) return GCG_OK;
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      n, p, g, m, v, step_dev, beta1, beta2, eps);
+  GCG_HIP_CHECK(hipGetLastError());
+  return GCG_OK;
+}
+
+gcg_status gcg_adamax_step_f32(int64_t n, float* p, const float* g, float* m, float* u,
+                               const float* step_dev, float beta1, float beta2, float eps,
+                               gcg_stream_t stream) {
+  if (n < 0 || (n > 0 && (p == nullptr || g == nullptr || m == nullptr || u == nullptr ||
+                          step_dev == nullptr)))
+    return fail(GCG_ERR_INVALID_ARG, "gcg_adamax_step_f32: bad arguments");
+  if (n == 0) return GCG_OK;
+  hipLaunchKernelGGL(adamax_kernel, dim3(grid_for(n)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), n, p, g, m, u, step_dev, beta1, beta2, eps);
   GCG_HIP_CHECK(hipGetLastError());
   return GCG_OK;
 }

@@ -2,6 +2,8 @@
 // 6 * C raw outputs read as a mixture of C bivariate Gaussians over (lat, lon). The fused
 // negative log-likelihood with its gradient, the reference's "mixture" / "pi" prediction rule,
 // and the transform of the raw outputs into (mus, sigmas, corxy, pis) the two are built from.
+// Below them the shared-component model (lang2loc_mdnshared.py) and, on its components, the
+// Gaussian layer of the inverse model (loc2lang.py) with its parameter gradients.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -637,6 +639,123 @@ size_t shared_nll_bytes(int64_t B, int64_t C) {
   return sizeof(float) * static_cast<size_t>((2 * kSharedPlanes + 5 * shared_groups(B)) * C + B);
 }
 
+// ---- the Gaussian layer of the inverse model (loc2lang.py:174; lasagne_layers.py:156-214) ---
+// The shared-component model's Gaussians as a layer: G[r][c] = the density of component c at the
+// coordinate of row r, and the gradient of the five parameter planes from an upstream dG.
+
+// One (row, component) in double: the exponent e = -0.5 z / q + k and what the five gradient
+// terms are built from. The difference x - mu is formed in double too (two float32 values:
+// exact), so that a parameter's sum over the rows keeps its meaning when an upstream dG of
+// either sign makes the rows cancel -- under the NLL the weights are responsibilities, all
+// positive, and float32 terms do (mdn_shared_nll_kernel).
+struct BigausTerm {
+  double u1, u2, z, e;
+};
+__device__ __forceinline__ BigausTerm bigaus_term(float x1, float x2, float m1, float m2,
+                                                  double s1, double s2, double rho, double q,
+                                                  double k) {
+  BigausTerm t;
+  t.u1 = (static_cast<double>(x1) - static_cast<double>(m1)) / s1;
+  t.u2 = (static_cast<double>(x2) - static_cast<double>(m2)) / s2;
+  t.z = (t.u1 * t.u1 + t.u2 * t.u2) - 2.0 * rho * (t.u1 * t.u2);
+  t.e = (-0.5 * t.z) / q + k;
+  return t;
+}
+
+constexpr int kLayerRows = 8;  // rows per workgroup of the forward
+
+// Thread t of workgroup (bx, by) owns component c = bx * 256 + t: its constants once, in double
+// and in mdn_shared_prep_kernel's expressions, then the row tiles by, by + gridDim.y, ... of 8
+// rows each. X is a broadcast load, G a coalesced store; a value depends on its row and
+// component alone. exp is double and G is rounded once.
+__global__ __launch_bounds__(kBlock) void bigaus_layer_kernel(
+    int64_t B, int C, const float* __restrict__ X, const float* __restrict__ mus,
+    const float* __restrict__ sig, const float* __restrict__ cor, float* __restrict__ G,
+    int64_t ldg) {
+  const int c = blockIdx.x * kBlock + threadIdx.x;
+  if (c >= C) return;
+  const double r1 = sig[2 * c], r2 = sig[2 * c + 1], a = fabs(static_cast<double>(cor[c]));
+  const double s1 = fmax(r1, 0.0) + log1p(exp(-fabs(r1)));
+  const double s2 = fmax(r2, 0.0) + log1p(exp(-fabs(r2)));
+  const double inv1 = 1.0 / (1.0 + a);
+  const double q = (1.0 + 2.0 * a) * (inv1 * inv1);
+  const double rho = cor[c] * inv1;
+  const double k = (-1.8378770664093453 - (log(s1) + log(s2))) - 0.5 * log(q);
+  const float m1 = mus[2 * c], m2 = mus[2 * c + 1];
+  for (int64_t r0 = static_cast<int64_t>(blockIdx.y) * kLayerRows; r0 < B;
+       r0 += static_cast<int64_t>(gridDim.y) * kLayerRows) {
+    const int64_t stop = std::min<int64_t>(r0 + kLayerRows, B);
+    for (int64_t r = r0; r < stop; ++r)
+      G[r * ldg + c] = static_cast<float>(
+          exp(bigaus_term(X[2 * r], X[2 * r + 1], m1, m2, s1, s2, rho, q, k).e));
+  }
+}
+
+// Workgroup g takes the rows [g R, (g + 1) R) of mdn_shared_nll_kernel's grouping; its thread t
+// (of 256) owns the components t, t + 256, ... and adds each one's five terms over the
+// workgroup's rows in row order, in double, the weight of a row being dG[r][c] * G[r][c] with G
+// recomputed as the forward computes it (P holds the constants mdn_shared_prep_kernel wrote).
+// X is a broadcast load, dG a coalesced one. One [5, C] partial of doubles per workgroup; no
+// sum crosses a thread here, so there is nothing to add between waves.
+__global__ __launch_bounds__(kBlock) void bigaus_layer_backward_kernel(
+    int64_t B, int C, int64_t R, const float* __restrict__ X, const float* __restrict__ mus,
+    const double* __restrict__ P, const float* __restrict__ dG, int64_t lddg,
+    double* __restrict__ partials) {
+  const int64_t r0 = static_cast<int64_t>(blockIdx.x) * R;
+  const int64_t r1 = std::min<int64_t>(r0 + R, B);
+  double* out = partials + static_cast<int64_t>(blockIdx.x) * 5 * C;
+  for (int c = threadIdx.x; c < C; c += kBlock) {
+    const double s1 = P[c], s2 = P[C + c], rho = P[2 * C + c], q = P[3 * C + c];
+    const double k = P[4 * C + c];
+    const float m1 = mus[2 * c], m2 = mus[2 * c + 1];
+    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0, acc4 = 0.0;
+    for (int64_t r = r0; r < r1; ++r) {
+      const BigausTerm t = bigaus_term(X[2 * r], X[2 * r + 1], m1, m2, s1, s2, rho, q, k);
+      const double w = static_cast<double>(dG[r * lddg + c]) * exp(t.e);
+      const double a1 = (t.u1 - rho * t.u2) / q, a2 = (t.u2 - rho * t.u1) / q;
+      acc0 = acc0 + w * (a1 / s1);
+      acc1 = acc1 + w * (a2 / s2);
+      acc2 = acc2 + w * ((t.u1 * a1 - 1.0) / s1);
+      acc3 = acc3 + w * ((t.u2 * a2 - 1.0) / s2);
+      acc4 = acc4 + w * ((t.u1 * t.u2 + rho * (1.0 - t.z / q)) / q);
+    }
+    out[c] = acc0;
+    out[C + c] = acc1;
+    out[2 * C + c] = acc2;
+    out[3 * C + c] = acc3;
+    out[4 * C + c] = acc4;
+  }
+}
+
+// dparams[j][c] = float32(factor_j(c) * (partial of workgroup 0 + 1 + ... in order)), the sum and
+// the factor in double: thread per (j, c).
+//   d mus: s; d sigmas_raw: s * sigmoid(raw); d corxy_raw: s / (1 + |raw|)^2
+__global__ __launch_bounds__(kBlock) void bigaus_layer_finish_kernel(
+    int C, int groups, const double* __restrict__ partials, const float* __restrict__ sig,
+    const float* __restrict__ cor, const float* __restrict__ scale_dev,
+    float* __restrict__ dparams) {
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= 5 * C) return;
+  double s = 0.0;
+  for (int g = 0; g < groups; ++g) s = s + partials[static_cast<int64_t>(g) * 5 * C + t];
+  const int j = t / C, c = t - j * C;
+  double f = scale_dev != nullptr ? static_cast<double>(*scale_dev) : 1.0;
+  if (j == 2 || j == 3) {
+    const double x = sig[2 * c + (j - 2)], e = exp(-fabs(x));
+    f = f * (x >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e));
+  }
+  if (j == 4) {
+    const double inv1 = 1.0 / (1.0 + fabs(static_cast<double>(cor[c])));
+    f = f * (inv1 * inv1);
+  }
+  dparams[t] = static_cast<float>(f * s);
+}
+
+// The workspace of gcg_bigaus_layer_backward_f32: P [5, C] and the partials [groups, 5, C], doubles.
+size_t bigaus_backward_bytes(int64_t B, int64_t C) {
+  return sizeof(double) * static_cast<size_t>((kSharedPlanes + 5 * shared_groups(B)) * C);
+}
+
 }  // namespace
 
 extern "C" {
@@ -815,6 +934,73 @@ gcg_status gcg_mdn_shared_predict_f32(int64_t B, int64_t C, const float* L, int6
   else if (C <= 2 * kBlock) GCG_MDN_SHARED_PREDICT(2);
   else GCG_MDN_SHARED_PREDICT(4);
 #undef GCG_MDN_SHARED_PREDICT
+  GCG_HIP_CHECK(hipGetLastError());
+  return GCG_OK;
+}
+
+gcg_status gcg_bigaus_layer_f32(int64_t B, int64_t C, const float* X, const float* mus,
+                                const float* sigmas_raw, const float* corxy_raw, float* G,
+                                int64_t ldg, gcg_stream_t stream) {
+  const char* fn = "gcg_bigaus_layer_f32";
+  if (gcg_status s = check_shared(fn, B, C, ldg)) return s;
+  if (B == 0) return GCG_OK;
+  if (X == nullptr || mus == nullptr || sigmas_raw == nullptr || corxy_raw == nullptr ||
+      G == nullptr)
+    return fail(GCG_ERR_INVALID_ARG, "%s: NULL operand", fn);
+  if (!aligned(X, 4) || !aligned(mus, 4) || !aligned(sigmas_raw, 4) || !aligned(corxy_raw, 4) ||
+      !aligned(G, 4))
+    return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B aligned", fn);
+  const unsigned tiles = static_cast<unsigned>(
+      std::min<int64_t>((B + kLayerRows - 1) / kLayerRows, 65535));
+  hipLaunchKernelGGL(bigaus_layer_kernel,
+                     dim3(static_cast<unsigned>((C + kBlock - 1) / kBlock), tiles), dim3(kBlock),
+                     0, static_cast<hipStream_t>(stream), B, static_cast<int>(C), X, mus,
+                     sigmas_raw, corxy_raw, G, ldg);
+  GCG_HIP_CHECK(hipGetLastError());
+  return GCG_OK;
+}
+
+gcg_status gcg_bigaus_layer_backward_f32_workspace_bytes(int64_t B, int64_t C, size_t* bytes) {
+  const char* fn = "gcg_bigaus_layer_backward_f32_workspace_bytes";
+  if (gcg_status s = check_shared(fn, B, C, C)) return s;
+  if (bytes == nullptr) return fail(GCG_ERR_INVALID_ARG, "%s: NULL bytes", fn);
+  *bytes = bigaus_backward_bytes(B, C);
+  return GCG_OK;
+}
+
+gcg_status gcg_bigaus_layer_backward_f32(int64_t B, int64_t C, const float* X, const float* mus,
+                                         const float* sigmas_raw, const float* corxy_raw,
+                                         const float* dG, int64_t lddg, const float* scale_dev,
+                                         float* dparams, void* workspace, size_t workspace_bytes,
+                                         gcg_stream_t stream) {
+  const char* fn = "gcg_bigaus_layer_backward_f32";
+  if (gcg_status s = check_shared(fn, B, C, lddg)) return s;
+  if (B == 0) return GCG_OK;
+  if (X == nullptr || mus == nullptr || sigmas_raw == nullptr || corxy_raw == nullptr ||
+      dG == nullptr || dparams == nullptr)
+    return fail(GCG_ERR_INVALID_ARG, "%s: NULL operand", fn);
+  if (!aligned(X, 4) || !aligned(mus, 4) || !aligned(sigmas_raw, 4) || !aligned(corxy_raw, 4) ||
+      !aligned(dG, 4) || !aligned(scale_dev, 4) || !aligned(dparams, 4) || !aligned(workspace, 8))
+    return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B (workspace: 8-B) aligned", fn);
+  if (workspace == nullptr || workspace_bytes < bigaus_backward_bytes(B, C))
+    return fail(GCG_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes "
+                "(gcg_bigaus_layer_backward_f32_workspace_bytes)", fn, workspace_bytes,
+                bigaus_backward_bytes(B, C));
+  const int c = static_cast<int>(C);
+  const int64_t R = shared_rows_per_group(B);
+  const int groups = static_cast<int>(shared_groups(B));
+  double* P = static_cast<double*>(workspace);
+  double* partials = P + kSharedPlanes * C;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(mdn_shared_prep_kernel, dim3(static_cast<unsigned>((C + kBlock - 1) / kBlock)),
+                     dim3(kBlock), 0, st, c, sigmas_raw, corxy_raw, P);
+  GCG_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(bigaus_layer_backward_kernel, dim3(groups), dim3(kBlock), 0, st, B, c, R, X,
+                     mus, P, dG, lddg, partials);
+  GCG_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(bigaus_layer_finish_kernel, dim3((5 * c + kBlock - 1) / kBlock),
+                     dim3(kBlock), 0, st, c, groups, partials, sigmas_raw, corxy_raw, scale_dev,
+                     dparams);
   GCG_HIP_CHECK(hipGetLastError());
   return GCG_OK;
 }

@@ -1,0 +1,708 @@
+"""The location-to-language model -- the reference's loc2lang.py (lat/lon to a word distribution).
+
+A coordinate goes through a layer of C trainable bivariate Gaussians (lasagne_layers.py:156-214),
+a rectified hidden layer and a softmax over the vocabulary, and is trained against each user's
+l1-normalised bag of words by categorical cross-entropy with Adamax (loc2lang.py:118-292).
+
+  bigaus_layer             G [B, C], the density of every component     gcg_bigaus_layer_f32,
+                           at every coordinate, differentiable in the   gcg_bigaus_layer_backward_f32
+                           three parameter tensors
+  BivariateGaussianLayer   the reference's layer: its defaults and draw order
+  softmax_xent_csr         mean cross-entropy of logits [M, V] against  gcg_softmax_xent_csr_f32
+                           rows of a CSR target, differentiable in the  (loss and gradient, one
+                           logits; the target is never densified        launch)
+  softmax_wide             softmax of rows of any width                 the same kernel
+  LasagneAdamax            lasagne.updates.adamax, one launch per       gcg_adamax_step_f32
+                           parameter
+  NNModel_loc2lang         the reference's class: constructor arguments, fit, predict
+  local_words              get_local_words (loc2lang.py:755-766) without the named-entity filter
+
+The transforms of the Gaussians' parameters and the order of every sum are stated in
+include/gcg_spmm.h.
+"""
+from __future__ import annotations
+
+import ctypes
+import logging
+from typing import Optional
+
+import numpy as np
+import scipy.sparse as sps
+import torch
+from torch.autograd.graph import increment_version
+
+from . import dense
+from . import sparse as gs
+from ._native import call
+from .layers import _as_tensor, _glorot_uniform
+from .mdn import MAX_COMPONENTS, _check_components, split_dparams
+from .mlp import n_batches
+from .sparse import _ptr, _stream_handle
+
+log = logging.getLogger(__name__)
+
+MAX_COLS = 1 << 24          # gcg_softmax_xent_csr_f32's widest row
+MAX_HIDDEN = 1024           # the rectify backward's one-pass kernel (sparse.relu_backward)
+EVAL_CHUNK_BYTES = 1 << 30  # a chunk's logits stay under this in evaluation and predict
+
+
+def _ld(t: torch.Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
+
+
+# -- the Gaussian layer ---------------------------------------------------------------------
+def _coords(X: torch.Tensor, dev) -> torch.Tensor:
+    gs._require_cuda(X, "X")
+    if X.dtype != torch.float32 or X.dim() != 2 or X.shape[1] != 2 or X.device != dev:
+        raise ValueError("X must be a float32 [B, 2] tensor (lat, lon) on the parameters' device")
+    return X.contiguous()
+
+
+def bigaus_forward(X: torch.Tensor, mus: torch.Tensor, sigmas_raw: torch.Tensor,
+                   corxy_raw: torch.Tensor) -> torch.Tensor:
+    """G [B, C] float32: the density of component c at the coordinate X[r] (one
+    gcg_bigaus_layer_f32 call; no autograd)."""
+    mus, sigmas_raw, corxy_raw = _check_components(mus, sigmas_raw, corxy_raw)
+    X = _coords(X, mus.device)
+    B, C, dev = X.shape[0], mus.shape[0], mus.device
+    G = gs.empty_dense(B, C, dev)
+    with torch.cuda.device(dev):
+        call("gcg_bigaus_layer_f32", B, C, _ptr(X), _ptr(mus), _ptr(sigmas_raw), _ptr(corxy_raw),
+             _ptr(G), _ld(G), _stream_handle(dev))
+    return G
+
+
+def bigaus_backward_workspace_bytes(B: int, C: int) -> int:
+    n = ctypes.c_size_t()
+    call("gcg_bigaus_layer_backward_f32_workspace_bytes", B, C, ctypes.byref(n))
+    return n.value
+
+
+def bigaus_backward(X: torch.Tensor, mus: torch.Tensor, sigmas_raw: torch.Tensor,
+                    corxy_raw: torch.Tensor, dG: torch.Tensor,
+                    scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dparams [5, C] (mdn.split_dparams' planes): the gradient of the three parameter tensors
+    from the upstream dG [B, C], times the device scalar `scale` when given (one
+    gcg_bigaus_layer_backward_f32 call)."""
+    mus, sigmas_raw, corxy_raw = _check_components(mus, sigmas_raw, corxy_raw)
+    X = _coords(X, mus.device)
+    B, C, dev = X.shape[0], mus.shape[0], mus.device
+    gs._require_cuda(dG, "dG")
+    if dG.dtype != torch.float32 or tuple(dG.shape) != (B, C) or dG.device != dev:
+        raise ValueError(f"dG must be a float32 [{B}, {C}] tensor on {dev}")
+    if C > 1 and dG.stride(1) != 1:
+        dG = dG.contiguous()
+    dparams = torch.empty((5, C), dtype=torch.float32, device=dev)
+    if B == 0:
+        return dparams.zero_()
+    nbytes = bigaus_backward_workspace_bytes(B, C)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    if scale is not None:
+        scale = scale.reshape(1).to(torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        call("gcg_bigaus_layer_backward_f32", B, C, _ptr(X), _ptr(mus), _ptr(sigmas_raw),
+             _ptr(corxy_raw), _ptr(dG), _ld(dG), _ptr(scale), _ptr(dparams), _ptr(ws), nbytes,
+             _stream_handle(dev))
+    return dparams
+
+
+class _BigausLayer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, mus, sigmas_raw, corxy_raw):
+        ctx.save_for_backward(X, mus, sigmas_raw, corxy_raw)
+        return bigaus_forward(X, mus, sigmas_raw, corxy_raw)
+
+    @staticmethod
+    def backward(ctx, dG):
+        dmus, dsig, dcor = split_dparams(bigaus_backward(*ctx.saved_tensors, dG))
+        return None, dmus, dsig, dcor
+
+
+def bigaus_layer(X: torch.Tensor, mus: torch.Tensor, sigmas_raw: torch.Tensor,
+                 corxy_raw: torch.Tensor) -> torch.Tensor:
+    """BivariateGaussianLayer.get_output_for (lasagne_layers.py:187-214): G [B, C], the density
+    of N(mus[c], softplus(sigmas_raw[c]), softsign(corxy_raw[c])) at X[r] (lat, lon),
+    differentiable in the three parameter tensors; X has no gradient (it is the network's
+    input)."""
+    return _BigausLayer.apply(X, mus, sigmas_raw, corxy_raw)
+
+
+class BivariateGaussianLayer(torch.nn.Module):
+    """lasagne_layers.BivariateGaussianLayer: num_units Gaussians over (lat, lon). Parameters not
+    given are drawn as the reference draws them, in its order, from NumPy's global stream:
+    mus = randn(C, 2), sigmas = 10 * ones(C, 2) (raw: sigma = softplus(.)), corxy = randn(C)
+    (raw: rho = softsign(.)) (lasagne_layers.py:164-178)."""
+
+    def __init__(self, num_units: int, mus=None, sigmas=None, corxy=None, device="cuda"):
+        super().__init__()
+        C = int(num_units)
+        if not 1 <= C <= MAX_COMPONENTS:
+            raise ValueError(f"num_units must be in [1, {MAX_COMPONENTS}], got {C}")
+        mus, sigmas, corxy = draw_components(C, mus, sigmas, corxy)
+        self.num_units = C
+        self.mus = torch.nn.Parameter(_as_tensor(mus, (C, 2), device))
+        self.sigmas = torch.nn.Parameter(_as_tensor(sigmas, (C, 2), device))
+        self.corxy = torch.nn.Parameter(_as_tensor(corxy, (C,), device))
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        return bigaus_layer(X, self.mus, self.sigmas, self.corxy)
+
+
+def draw_components(C: int, mus=None, sigmas=None, corxy=None):
+    """The layer's three initial arrays: those given, the others by lasagne_layers.py:164-178
+    (mus' draw before corxy's; sigmas takes none)."""
+    if mus is None:
+        mus = np.random.randn(C, 2).astype(np.float32)
+    if sigmas is None:
+        sigmas = np.array([10, 10], np.float32) * np.ones((C, 2), np.float32)
+    if corxy is None:
+        corxy = np.random.randn(C).reshape((C,)).astype(np.float32)
+    return mus, sigmas, corxy
+
+
+# -- softmax cross-entropy against sparse soft targets ------------------------------------------
+def check_targets(Y) -> sps.csr_matrix:
+    """A scipy sparse (or dense) target as the canonical-column CSR the kernel needs, float32,
+    checked on the host: every column in [0, n_cols) and no column twice in a row (the kernel
+    subtracts a row's entries in place; of two on one column one would be lost). ValueError
+    otherwise -- nothing is summed or dropped silently."""
+    if not sps.issparse(Y):
+        Y = sps.csr_matrix(np.asarray(Y, dtype=np.float32))
+    Y = Y.tocsr() if Y.format != "csr" else Y
+    indptr, indices = np.asarray(Y.indptr), np.asarray(Y.indices)
+    if indptr.size != Y.shape[0] + 1 or indptr[0] != 0 or indptr[-1] != indices.size or \
+            (np.diff(indptr) < 0).any():
+        raise ValueError("target CSR: indptr must be monotone from 0 to nnz")
+    if indices.size and (indices.min() < 0 or indices.max() >= Y.shape[1]):
+        raise ValueError(f"target CSR: a column index is outside [0, {Y.shape[1]})")
+    row_of = np.repeat(np.arange(Y.shape[0]), np.diff(indptr))
+    key = row_of.astype(np.int64) * Y.shape[1] + indices
+    if np.unique(key).size != key.size:
+        raise ValueError("target CSR: a row holds the same column twice (sum_duplicates() first)")
+    return sps.csr_matrix((np.asarray(Y.data, dtype=np.float32), indices.astype(np.int32),
+                           indptr.astype(np.int32)), shape=Y.shape)
+
+
+def target_csr(Y, device="cuda") -> gs.DeviceCSR:
+    """Upload a target matrix once: check_targets on the host, then DeviceCSR (validated on the
+    device as every DeviceCSR is), marked as free of duplicate columns."""
+    if isinstance(Y, gs.DeviceCSR):
+        return _checked(Y)
+    Yd = gs.DeviceCSR.from_scipy(check_targets(Y), device)
+    Yd._rows_unique = True
+    return Yd
+
+
+def _checked(Y: gs.DeviceCSR) -> gs.DeviceCSR:
+    """A DeviceCSR built elsewhere: its rows checked for duplicate columns once, on the device
+    (one synchronisation, remembered on the object)."""
+    if getattr(Y, "_rows_unique", None) is None:
+        unique = True
+        if Y.nnz > 1:
+            counts = (Y.indptr[1:] - Y.indptr[:-1]).to(torch.int64)
+            row_of = torch.repeat_interleave(torch.arange(Y.n_rows, device=Y.device), counts)
+            key = row_of * Y.n_cols + Y.indices.to(torch.int64)
+            unique = int(torch.unique(key).numel()) == Y.nnz
+        Y._rows_unique = unique
+    if not Y._rows_unique:
+        raise ValueError("target CSR: a row holds the same column twice")
+    return Y
+
+
+def check_rows(rows, y_rows: int, M: int) -> np.ndarray:
+    """Host-side row ids of the target, one per logits row, as int32: ValueError unless there
+    are M of them, all in [0, y_rows)."""
+    rows = np.asarray(rows)
+    if rows.ndim != 1 or rows.size != M or rows.dtype.kind not in "iu":
+        raise ValueError(f"rows must be {M} integer row ids of the target")
+    if rows.size and (rows.min() < 0 or rows.max() >= y_rows):
+        raise ValueError(f"rows: a row id is outside [0, {y_rows})")
+    return np.ascontiguousarray(rows, dtype=np.int32)
+
+
+def _device_rows(rows, Y: gs.DeviceCSR, M: int) -> Optional[torch.Tensor]:
+    """rows as the kernel takes them. A host array is validated here; a device tensor is taken
+    as it is (the kernel gives a row id out of range a NaN loss, never an index)."""
+    if rows is None:
+        if Y.n_rows < M:
+            raise ValueError(f"the target has {Y.n_rows} rows, the logits {M}")
+        return None
+    if isinstance(rows, torch.Tensor) and rows.is_cuda:
+        if rows.dtype != torch.int32 or rows.dim() != 1 or rows.numel() != M or \
+                rows.device != Y.device:
+            raise ValueError(f"device rows must be {M} int32 row ids on the target's device")
+        return rows.contiguous()
+    if isinstance(rows, torch.Tensor):
+        rows = rows.numpy()
+    return torch.from_numpy(check_rows(rows, Y.n_rows, M)).to(Y.device)
+
+
+def _check_logits(logits: torch.Tensor) -> torch.Tensor:
+    gs._require_cuda(logits, "logits")
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise ValueError("logits must be a float32 [M, N] tensor")
+    if not 1 <= logits.shape[1] <= MAX_COLS:
+        raise ValueError(f"logits must have 1 .. {MAX_COLS} columns")
+    return logits if logits.shape[1] == 1 or logits.stride(1) == 1 else logits.contiguous()
+
+
+def xent_csr_forward_backward(logits: torch.Tensor, Y: gs.DeviceCSR,
+                              rows: Optional[torch.Tensor] = None, scale: float = 1.0,
+                              scale_dev: Optional[torch.Tensor] = None, want_grad: bool = True,
+                              in_place: bool = False):
+    """(loss_rows [M], dlogits or None) from one gcg_softmax_xent_csr_f32 call.
+    loss_rows[i] = -sum_j Y[rows[i]][j] log softmax(logits[i])_j; dlogits = scale * *scale_dev *
+    d loss_rows[i] / d logits[i] (None unless want_grad; in_place: written over the logits).
+    rows: int32 device row ids of Y (None: row i), Y: a target_csr(...)."""
+    logits = _check_logits(logits)
+    M, N = logits.shape
+    if Y.n_cols != N or Y.device != logits.device:
+        raise ValueError(f"the target must be [*, {N}] on {logits.device}")
+    dev = logits.device
+    loss_rows = torch.empty(M, dtype=torch.float32, device=dev)
+    out = None
+    if want_grad:
+        out = logits if in_place else gs.empty_dense(M, N, dev)
+    if scale_dev is not None:
+        scale_dev = scale_dev.reshape(1).to(torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        call("gcg_softmax_xent_csr_f32", M, N, _ptr(logits), _ld(logits), Y.n_rows,
+             _ptr(Y.indptr), _ptr(Y.indices), _ptr(Y.data), _ptr(rows), float(scale),
+             _ptr(scale_dev), _ptr(out), _ld(out) if out is not None else 0, _ptr(loss_rows),
+             _stream_handle(dev))
+    return loss_rows, out
+
+
+class _SoftmaxXentCSR(torch.autograd.Function):
+    """The forward launch already writes the gradient of the mean (upstream 1); backward scales
+    it by the upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, Y, rows, denom):
+        want = ctx.needs_input_grad[0]
+        loss_rows, dZ = xent_csr_forward_backward(logits, Y, rows, scale=1.0 / denom,
+                                                  want_grad=want)
+        ctx.dZ = dZ
+        return loss_rows.sum() / denom
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.dZ * g, None, None, None
+
+
+def softmax_xent_csr(logits: torch.Tensor, Y: gs.DeviceCSR, rows=None,
+                     denom: Optional[int] = None) -> torch.Tensor:
+    """lasagne.objectives.categorical_crossentropy(softmax(logits), Y[rows]).sum() / denom
+    (loc2lang.py:193-194; denom defaults to the M rows: the mean) as a device scalar,
+    differentiable in the logits. Y: the soft targets as a DeviceCSR (target_csr: columns in
+    range, none twice in a row), never densified; rows: one row id of Y per logits row -- a host
+    array (validated: ValueError before any launch) or int32 device tensor; None pairs row i
+    with row i. Written as sum_k y_k (logsumexp(z) - z_k): the reference's -sum y log p wherever
+    that is finite."""
+    Y = target_csr(Y)
+    logits = _check_logits(logits)
+    M = logits.shape[0]
+    rows = _device_rows(rows, Y, M)
+    return _SoftmaxXentCSR.apply(logits, Y, rows, float(max(M if denom is None else denom, 1)))
+
+
+def softmax_wide(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Row softmax of logits [M, N] of any width up to 2^24 (dense.softmax stops at 4096
+    columns): gcg_softmax_xent_csr_f32 without a target. out may be the logits."""
+    logits = _check_logits(logits)
+    M, N = logits.shape
+    if out is None:
+        out = gs.empty_dense(M, N, logits.device)
+    with torch.cuda.device(logits.device):
+        call("gcg_softmax_xent_csr_f32", M, N, _ptr(logits), _ld(logits), 0, None, None, None,
+             None, 1.0, None, _ptr(out), _ld(out), None, _stream_handle(logits.device))
+    return out
+
+
+# -- Adamax -------------------------------------------------------------------------------------
+class LasagneAdamax:
+    """lasagne.updates.adamax: t += 1; a_t = lr/(1-b1^t); m = b1*m + (1-b1)*g;
+    u = max(b2*u, |g|); p -= a_t*m/(u+eps). mlpconv.LasagneAdam's interface."""
+
+    def __init__(self, params, lr=2e-3, beta1=0.9, beta2=0.999, epsilon=1e-8):
+        self.params = list(params)
+        self.lr, self.beta1, self.beta2, self.eps = lr, beta1, beta2, epsilon
+        self.t = 0
+        self.m = [torch.zeros_like(p) for p in self.params]
+        self.u = [torch.zeros_like(p) for p in self.params]
+        # a_t lives on the device, as LasagneAdam's
+        self.a_t = torch.zeros((), dtype=torch.float32, device=self.params[0].device)
+
+    def prepare(self):
+        """Host half of a step: t += 1 and the bias-corrected step size (Python double, rounded
+        once to float32)."""
+        self.t += 1
+        self.a_t.fill_(self.lr / (1 - self.beta1 ** self.t))
+
+    @torch.no_grad()
+    def apply(self):
+        """Device half of a step: one fused launch per parameter (gcg_adamax_step_f32)."""
+        for p, m, u in zip(self.params, self.m, self.u):
+            g = p.grad.contiguous()
+            if not p.is_contiguous():
+                raise ValueError("LasagneAdamax needs contiguous parameters")
+            with torch.cuda.device(p.device):
+                call("gcg_adamax_step_f32", p.numel(), _ptr(p), _ptr(g), _ptr(m), _ptr(u),
+                     _ptr(self.a_t), self.beta1, self.beta2, self.eps, _stream_handle(p.device))
+            # an in-place write through a raw pointer: bump the version counters as a torch
+            # in-place op would, so the padded weight copies (dense._WeightCache) follow
+            increment_version(p)
+            increment_version(m)
+            increment_version(u)
+
+    def step(self):
+        self.prepare()
+        self.apply()
+
+    def state(self):
+        return {"t": self.t, "m": [x.clone() for x in self.m], "u": [x.clone() for x in self.u]}
+
+    @torch.no_grad()
+    def load_state(self, st):
+        self.t = st["t"]
+        for dst, src in zip(self.m + self.u, st["m"] + st["u"]):
+            dst.copy_(src)
+
+    def zero_grad(self):
+        for p in self.params:
+            p.grad = None
+
+
+# -- the model ------------------------------------------------------------------------------
+class NNModel_loc2lang:
+    """loc2lang.NNModel (loc2lang.py:118-292) with every product, the Gaussian layer, the loss
+    and the update on the GPU.
+
+    Network: G = bigaus_layer(X) with n_gaus_comp components; relu(G.Wh + bh) with hid_size
+    units when hid_size is non-zero; the linear projection to output_size logits whose softmax
+    is folded into the loss. GlorotUniform weights and zero biases, drawn in Lasagne's
+    construction order on NumPy's global stream: the layer's mus and corxy (each only when the
+    constructor was not given it), Wh, Wo. The parameter list has get_all_param_values' order
+    [mus, sigmas, corxy, (Wh, bh,) Wo, bo] (get_params, set_params, init_parameters).
+    Loss: softmax_xent_csr against the rows' l1-normalised bags of words, held on the device as
+    one CSR per split and never densified. Adamax, lr 2e-3, on every parameter.
+
+    One epoch (loc2lang.py:246-273): shuffled batches with the tail dropped; a batch's target
+    rows are reached through their row ids (no slice of Y per batch); the reported train loss
+    is the mean of the batch losses (each before its update), accumulated on the device; no host
+    synchronisation between an epoch's first and last batch. The dev loss is the mean over all
+    dev rows (loc2lang.py:257: no tail drop). A dev loss is kept when
+    l_val < best and best - l_val > 1e-4 l_val; otherwise a counter runs and training stops when
+    it exceeds early_stopping_max_down; the best parameters are restored. fit returns
+    (perplexity_test, perplexity_dev) = 2 ** loss with the natural-log loss, as the reference
+    computes it.
+
+    Step: the Gaussian layer, the two NT GEMMs (rectify in the first one's epilogue),
+    gcg_softmax_xent_csr_f32 (losses, and the gradient written over the logits), the weight
+    gradients (TN GEMMs) and input gradients (NT GEMMs), the rectify backward with its column
+    sums, gcg_bigaus_layer_backward_f32, one Adamax launch per parameter.
+
+    Deviations. The loss is evaluated as sum y (logsumexp - z), finite where the reference's
+    log(softmax) underflows to -inf. Evaluation and predict run in row chunks whose logits stay
+    under 1 GiB, the row losses added in row order in float64 (the reference evaluates a split
+    in one call). When no epoch satisfies the selection rule (n_epochs = 0, or a NaN loss) the
+    last parameters are kept, where the reference would pass None to set_all_param_values and
+    crash. The rectify passes no gradient at a pre-activation of exactly 0 (Theano: half).
+    nomdn=True, a truthy reload, sparse (grid) inputs and a dtype other than float32 are
+    refused; regul_coef, drop_out, dropout_coef and autoencoder are accepted and unused, as the
+    reference's build uses none of them (no penalty and no dropout exist in what it executes).
+    """
+
+    def __init__(self, n_epochs=10, batch_size=1000, regul_coef=1e-6, input_size=None,
+                 output_size=None, hid_size=500, drop_out=False, dropout_coef=0.5,
+                 early_stopping_max_down=10, dtype="float32", autoencoder=100, reload=False,
+                 n_gaus_comp=500, mus=None, sigmas=None, corxy=None, nomdn=False,
+                 dataset_name="", init_parameters=None, device="cuda"):
+        if nomdn:
+            raise NotImplementedError("nomdn (a rectified dense layer in place of the Gaussians) "
+                                      "is not built")
+        if reload:
+            raise NotImplementedError("reload (a pickled model file) is not built")
+        if dtype != "float32":
+            raise ValueError("the GPU path computes in float32 (loc2lang.py dtype='float32')")
+        if input_size is not None and int(input_size) != 2:
+            raise NotImplementedError("the input is a coordinate [lat, lon] (input_size 2); the "
+                                      "grid representation is not built")
+        if not 1 <= int(n_gaus_comp) <= MAX_COMPONENTS:
+            raise ValueError(f"n_gaus_comp must be in [1, {MAX_COMPONENTS}]")
+        if not 0 <= int(hid_size) <= MAX_HIDDEN:
+            raise ValueError(f"hid_size must be in [0, {MAX_HIDDEN}]")
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be positive")
+        C = int(n_gaus_comp)
+        for x, shape, name in ((mus, (C, 2), "mus"), (sigmas, (C, 2), "sigmas"),
+                               (corxy, (C,), "corxy")):
+            if x is not None and np.shape(x) != shape:
+                raise ValueError(f"{name} must have shape {shape}, got {np.shape(x)}")
+        self.n_epochs = n_epochs
+        self.batch_size = int(batch_size)
+        self.regul_coef = regul_coef
+        self.hid_size = int(hid_size)
+        self.drop_out = drop_out
+        self.dropout_coef = dropout_coef
+        self.early_stopping_max_down = early_stopping_max_down
+        self.dtype = dtype
+        self.input_size = 2
+        self.output_size = None if output_size is None else int(output_size)
+        self.autoencoder = autoencoder
+        self.reload = False
+        self.n_gaus_comp = C
+        self.mus_init, self.sigmas_init, self.corxy_init = mus, sigmas, corxy
+        self.nomdn = False
+        self.dataset_name = dataset_name
+        self.init_parameters = init_parameters
+        self.device = torch.device(device)
+        self.history = []
+        self.params = None
+        if self.output_size is not None:  # the reference builds in its constructor
+            self._build(self.output_size)
+
+    # -- model --------------------------------------------------------------------------
+    @property
+    def names(self):
+        return ["mus", "sigmas", "corxy"] + (["Wh", "bh"] if self.hid_size else []) + ["Wo", "bo"]
+
+    def _param(self, x, shape):
+        return torch.nn.Parameter(_as_tensor(x, shape, self.device), requires_grad=False)
+
+    def _build(self, V: int):
+        if not 1 <= V <= MAX_COLS:
+            raise ValueError(f"output_size must be in [1, {MAX_COLS}]")
+        C, K = self.n_gaus_comp, self.hid_size
+        init = self.init_parameters
+        if init is not None:
+            if len(init) != len(self.names):
+                raise ValueError(f"init_parameters must be [{', '.join(self.names)}], as "
+                                 "lasagne.layers.get_all_param_values gives them")
+            init = list(init)
+        else:  # Lasagne's construction order: the Gaussian layer, the hidden layer, the output
+            init = list(draw_components(C, self.mus_init, self.sigmas_init, self.corxy_init))
+            if K:
+                init += [_glorot_uniform(C, K), np.zeros(K, np.float32)]
+            init += [_glorot_uniform(K or C, V), np.zeros(V, np.float32)]
+        shapes = [(C, 2), (C, 2), (C,)] + ([(C, K), (K,)] if K else []) + [(K or C, V), (V,)]
+        self.params = [self._param(x, s) for x, s in zip(init, shapes)]
+        self.mus, self.sigmas, self.corxy = self.params[:3]
+        self.Wh, self.bh = (self.params[3], self.params[4]) if K else (None, None)
+        self.Wo, self.bo = self.params[-2], self.params[-1]
+        self._proj_h, self._proj_o = dense.Projection(), dense.Projection()
+        self.output_size = V
+        self.optimizer = LasagneAdamax(self.params, lr=2e-3, beta1=0.9, beta2=0.999,
+                                       epsilon=1e-8)
+
+    def _features(self, x: torch.Tensor):
+        """(G, H): the Gaussian layer's output and the last layer before the projection."""
+        G = bigaus_forward(x, self.mus, self.sigmas, self.corxy)
+        if not self.hid_size:
+            return G, G
+        return G, dense.gemm_nt(G, self._proj_h.fwd.get(self.Wh, True), bias=self.bh, act="relu")
+
+    def _logits(self, x: torch.Tensor) -> torch.Tensor:
+        H = self._features(x)[1]
+        return dense.gemm_nt(H, self._proj_o.fwd.get(self.Wo, True), bias=self.bo)
+
+    def _chunk_rows(self) -> int:
+        return max(1, EVAL_CHUNK_BYTES // (4 * gs.row_stride(self.output_size)) - 1)
+
+    def _to_coords(self, X, name: str = "X") -> torch.Tensor:
+        if sps.issparse(X) or isinstance(X, gs.DeviceCSR):
+            raise NotImplementedError("the input is a dense [n, 2] coordinate array; the sparse "
+                                      "grid representation is not built")
+        if isinstance(X, torch.Tensor):
+            X = X.detach().cpu().numpy()
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] != 2:
+            raise ValueError(f"{name} must have shape (n, 2) [lat, lon], got {X.shape}")
+        return torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(self.device)
+
+    @torch.no_grad()
+    def _evaluate(self, x: torch.Tensor, Y: gs.DeviceCSR) -> float:
+        """f_val (loc2lang.py:210, 257): the mean loss over every row of a split, in row chunks;
+        the row losses are added in row order, in float64, on the host (one synchronisation)."""
+        n, step = x.shape[0], self._chunk_rows()
+        rows_all = torch.arange(n, dtype=torch.int32, device=self.device)
+        losses = torch.empty(n, dtype=torch.float32, device=self.device)
+        for a in range(0, n, step):
+            b = min(a + step, n)
+            losses[a:b] = xent_csr_forward_backward(self._logits(x[a:b]), Y, rows_all[a:b],
+                                                    want_grad=False)[0]
+        return float(np.cumsum(losses.cpu().numpy().astype(np.float64))[-1] / n)
+
+    # -- training -----------------------------------------------------------------------
+    def _prepare_epoch(self, order) -> None:
+        """Host half of an epoch: the order checked to be a permutation, cut into whole batches
+        and uploaded; its coordinates gathered once."""
+        n, B = self._x_train.shape[0], self.batch_size
+        order = np.asarray(order)
+        if order.ndim != 1 or order.size != n or \
+                not np.array_equal(np.sort(order), np.arange(n)):
+            raise ValueError(f"an epoch's order must be a permutation of the {n} training rows")
+        self._n_batches = n_batches(n, B)
+        perm = np.ascontiguousarray(order[:self._n_batches * B], dtype=np.int32)
+        self._perm = torch.from_numpy(perm).to(self.device)
+        self._x_epoch = self._x_train.index_select(0, self._perm.to(torch.int64))
+
+    @torch.no_grad()
+    def _step(self, x: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+        """One batch: the loss (device scalar) and the gradients of every parameter, then the
+        Adamax update."""
+        B, opt = x.shape[0], self.optimizer
+        G, H = self._features(x)
+        Z = dense.gemm_nt(H, self._proj_o.fwd.get(self.Wo, True), bias=self.bo)
+        loss_rows, dZ = xent_csr_forward_backward(Z, self._y_train, rows, scale=1.0 / B,
+                                                  in_place=True)
+        loss = loss_rows.sum() / B
+        self.Wo.grad = dense.gemm_tn(H, dZ)
+        self.bo.grad = dZ.sum(dim=0) if dZ.shape[1] > 1024 else gs.colsum(dZ)
+        dH = dense.gemm_nt(dZ, self._proj_o.bwd.get(self.Wo, False))
+        if self.hid_size:
+            g, self.bh.grad = gs.relu_backward(dH, Y=H, out=dH)
+            self.Wh.grad = dense.gemm_tn(G, g)
+            dG = dense.gemm_nt(g, self._proj_h.bwd.get(self.Wh, False))
+        else:
+            dG = dH
+        dparams = bigaus_backward(x, self.mus, self.sigmas, self.corxy, dG)
+        self.mus.grad, self.sigmas.grad, self.corxy.grad = split_dparams(dparams)
+        opt.step()
+        return loss
+
+    @torch.no_grad()
+    def _run_batches(self) -> torch.Tensor:
+        """Device half of an epoch: every batch's step, no host synchronisation. Returns the
+        mean of the batch losses as a device scalar."""
+        B = self.batch_size
+        total = torch.zeros((), dtype=torch.float32, device=self.device)
+        self.batch_losses = []
+        for b in range(self._n_batches):
+            loss = self._step(self._x_epoch[b * B:(b + 1) * B], self._perm[b * B:(b + 1) * B])
+            self.batch_losses.append(loss)
+            total += loss
+        return total / self._n_batches
+
+    def _train_epoch(self, order=None) -> torch.Tensor:
+        if order is None:  # loc2lang.py:219-221, numpy's global stream
+            order = np.arange(self._x_train.shape[0])
+            np.random.shuffle(order)
+        self._prepare_epoch(order)
+        return self._run_batches()
+
+    def _split(self, X, Y, name: str):
+        x = self._to_coords(X, name)
+        Yd = target_csr(Y, self.device)
+        if Yd.n_rows != x.shape[0]:
+            raise ValueError(f"X_{name} has {x.shape[0]} rows, Y_{name} {Yd.n_rows}")
+        return x, Yd
+
+    @torch.no_grad()
+    def fit(self, X_train, Y_train, X_dev, Y_dev, X_test, Y_test, epoch_orders=None):
+        """loc2lang.py:229-288. X_*: [n, 2] coordinate arrays (lat, lon); Y_*: the rows' bags of
+        words, scipy sparse or dense [n, V], uploaded once as CSR. Returns
+        (perplexity_test, perplexity_dev). epoch_orders (tests, measurement): one permutation of
+        the training rows per epoch instead of the np.random.shuffle draws."""
+        self._x_train, self._y_train = self._split(X_train, Y_train, "train")
+        x_dev, y_dev = self._split(X_dev, Y_dev, "dev")
+        x_test, y_test = self._split(X_test, Y_test, "test")
+        V = self._y_train.n_cols
+        if y_dev.n_cols != V or y_test.n_cols != V:
+            raise ValueError("Y_train, Y_dev and Y_test differ in width")
+        if self.params is None:
+            self._build(V)
+        elif self.output_size != V:
+            raise ValueError(f"Y_train has {V} columns, output_size says {self.output_size}")
+        n_batches(self._x_train.shape[0], self.batch_size)  # n < B raises
+        if x_dev.shape[0] == 0 or x_test.shape[0] == 0:
+            raise ValueError("the dev and test splits need at least one row")
+        log.info("training with %d n_epochs and %d batch_size", self.n_epochs, self.batch_size)
+        self.history, self.epoch_batch_losses = [], []
+        best_params, best_val_loss, n_down = None, float("inf"), 0
+        for n in range(self.n_epochs):
+            order = None if epoch_orders is None else epoch_orders[n]
+            l_train = self._train_epoch(order)
+            l_val = self._evaluate(x_dev, y_dev)
+            l_train = float(l_train)
+            self.epoch_batch_losses.append(torch.stack(self.batch_losses).cpu().numpy())
+            stop = False
+            if l_val < best_val_loss and (best_val_loss - l_val) > (0.0001 * l_val):
+                best_val_loss, n_down = l_val, 0
+                best_params = [p.detach().clone() for p in self.params]
+            else:
+                n_down += 1
+                stop = n_down > self.early_stopping_max_down
+            self.history.append({"epoch": n, "train_loss": l_train, "val_loss": l_val})
+            if stop:
+                log.info("validation results went down. early stopping ...")
+                break
+            log.info("iter %d, train loss %f, dev loss %f, best dev loss %f, num_down %d", n,
+                     l_train, l_val, best_val_loss, n_down)
+        self.last_params = [p.detach().cpu().numpy() for p in self.params]
+        if best_params is not None:  # None: no epoch qualified; keep the last parameters
+            self.set_params(best_params)
+        self.best_val_loss = best_val_loss
+        l_test = self._evaluate(x_test, y_test)
+        l_dev = self._evaluate(x_dev, y_dev)
+        self.test_loss, self.dev_loss = l_test, l_dev
+        log.info("test loss is %f and perplexity is %f", l_test, np.power(2, l_test))
+        log.info("dev loss is %f and perplexity is %f", l_dev, np.power(2, l_dev))
+        return np.power(2, l_test), np.power(2, l_dev)
+
+    # -- reference API ------------------------------------------------------------------
+    def _built(self):
+        if self.params is None:
+            raise RuntimeError("the model has no parameters yet: give output_size or call fit")
+
+    @torch.no_grad()
+    def predict(self, X) -> np.ndarray:
+        """f_predict_proba (loc2lang.py:290-292): [n, V] word probabilities for every row of X,
+        as a NumPy array, computed in row chunks."""
+        self._built()
+        x = self._to_coords(X)
+        n, step = x.shape[0], self._chunk_rows()
+        out = np.empty((n, self.output_size), np.float32)
+        for a in range(0, n, step):
+            Z = self._logits(x[a:a + step])
+            out[a:a + step] = softmax_wide(Z, out=Z).cpu().numpy()
+        return out
+
+    @torch.no_grad()
+    def gaus_output(self, X) -> np.ndarray:
+        """f_gaus (loc2lang.py:208): the Gaussian layer's output [n, n_gaus_comp]."""
+        self._built()
+        return bigaus_forward(self._to_coords(X), self.mus, self.sigmas, self.corxy).cpu().numpy()
+
+    def get_params(self):
+        self._built()
+        return [p.detach().cpu().numpy() for p in self.params]
+
+    def set_params(self, params):
+        """loc2lang.py:214-215."""
+        self._built()
+        if len(params) != len(self.params):
+            raise ValueError(f"expected [{', '.join(self.names)}]")
+        with torch.no_grad():
+            for p, v in zip(self.params, params):
+                p.copy_(_as_tensor(v, tuple(p.shape), self.device))
+
+
+NNModel = NNModel_loc2lang  # the reference's name for it
+
+
+def local_words(preds, k: int = 50) -> np.ndarray:
+    """get_local_words (loc2lang.py:755-766) without the vocabulary and the named-entity filter:
+    the columns of preds [n, V] (a word's probability at n places) are l1-normalised over the
+    rows, each column's entropy is taken (scipy.stats.entropy: natural log, 0 log 0 = 0), and
+    the indices of the k lowest entropies are returned in ascending order of entropy (stable).
+    Plain torch, float64: not a hot path."""
+    p = torch.as_tensor(np.asarray(preds) if not isinstance(preds, torch.Tensor) else preds)
+    if p.dim() != 2:
+        raise ValueError("preds must be [n, V]")
+    p = p.to(torch.float64)
+    norm = p.abs().sum(dim=0, keepdim=True)
+    p = p / torch.where(norm == 0, torch.ones_like(norm), norm)  # sklearn leaves a zero column
+    ent = -torch.special.xlogy(p, p).sum(dim=0)
+    ent = torch.where(norm[0] == 0, torch.full_like(ent, float("nan")), ent)  # entropy of 0 / 0
+    return torch.argsort(ent, stable=True)[:int(k)].cpu().numpy()

@@ -343,6 +343,17 @@ gcg_status gcg_adam_step_f32(int64_t n, float* p, const float* g, float* m, floa
                              gcg_stream_t stream);
 
 /*
+ * lasagne.updates.adamax (loc2lang.py:207) for one float32 parameter of n elements, in place and
+ * in one pass:
+ *   m = b1*m + (1-b1)*g;  u = max(b2*u, |g|);  p -= a_t*m / (u + eps),
+ * with a_t = lr/(1-b1^t) read from the device scalar *step_dev, as gcg_adam_step_f32 reads its
+ * step size. Returns GCG_OK without a launch when n == 0.
+ */
+gcg_status gcg_adamax_step_f32(int64_t n, float* p, const float* g, float* m, float* u,
+                               const float* step_dev, float beta1, float beta2, float eps,
+                               gcg_stream_t stream);
+
+/*
  * The weight penalty of the MLPCONV loss (mlpconv.py:235-243: lasagne.regularization l1 =
  * sum|W|, l2 = sum W^2, scaled by regul_coef * share) for one float32 weight of n elements:
  *   *out = ((acc_in ? *acc_in : 0) + l1 * sum|W|) + l2 * sum W^2
@@ -565,6 +576,94 @@ gcg_status gcg_mdn_shared_predict_f32(int64_t B, int64_t C, const float* L, int6
                                       const float* Dt /*nullable for method 1*/,
                                       const float* mus, int method, int32_t* idx /*nullable*/,
                                       float* latlon, gcg_stream_t stream);
+
+/*
+ * The Gaussian layer of the inverse model (reference loc2lang.py:174; lasagne_layers.py:156-214,
+ * BivariateGaussianLayer): the C Gaussians of the shared-component model above -- the same three
+ * parameter tensors, transforms and stable forms, 1 <= C <= 1024 -- as a layer over coordinates
+ * X (B x 2 float32, contiguous: lat, lon). With u_i = (x_i - mus[c][i]) / s_i,
+ *     z = u1^2 + u2^2 - 2 rho u1 u2
+ *     G[r][c] = exp(-log(2 pi) - log s1 - log s2 - 0.5 log q - 0.5 z / q)
+ * the reference's log-domain form (lasagne_layers.py:207-212). Both calls compute in double from
+ * the float32 inputs -- the constants once per component from the raw parameters, and per
+ * element the difference x - mu (exact), u, z, the exponent, the exponential and the gradient
+ * terms -- and round a result to float32 once. Unlike the responsibilities of the NLL, an
+ * upstream dG has either sign, and a parameter's sum over the rows may cancel by orders of
+ * magnitude; float32 terms would leave their rounding in what remains. The calls validate on the
+ * host, allocate nothing, use no atomics, and return GCG_OK without a launch when B == 0.
+ *
+ * gcg_bigaus_layer_f32: G (B x C, row stride ldg >= C). G[r][c] depends on row r and component
+ * c alone, not on B, ldg or the grid.
+ *
+ * gcg_bigaus_layer_backward_f32: dparams receives the gradient of the three parameter tensors
+ * from an upstream dG (B x C, row stride lddg >= C), in gcg_mdn_shared_nll_f32's five planes of
+ * C (d mus lat, d mus lon, d sigmas_raw lat, d sigmas_raw lon, d corxy_raw). G is recomputed as
+ * the forward computes it, so no stride of it needs agreeing. With a_1 = (u1 - rho u2) / q,
+ * a_2 = (u2 - rho u1) / q the sums over the rows are
+ *     sum_r dG G a_i / s_i,   sum_r dG G (u_i a_i - 1) / s_i,
+ *     sum_r dG G (u1 u2 + rho (1 - z / q)) / q
+ * times s, s * sigmoid(sigmas_raw), s / (1 + |corxy_raw|)^2, s = *scale_dev or 1 when NULL, the
+ * factors applied once after the sum. X has no gradient. The order of every sum is fixed: the
+ * rows are grouped as in gcg_mdn_shared_nll_f32, R = 4 * max(1, ceil(B / 2048)) rows per
+ * workgroup (a function of B alone; at most 512 workgroups), workgroup g the rows
+ * [g R, (g + 1) R). Within a workgroup a component belongs to one thread, which adds its terms
+ * over the workgroup's rows in row order -- the double accumulators of all components do not fit
+ * a wave's registers at C = 1024, so the components, not the rows, are spread over the four
+ * waves and no sum crosses a wave. A second launch adds the workgroups' partials in ascending g,
+ * applies the factor and rounds to float32. dparams is reproducible bit for bit.
+ * workspace: gcg_bigaus_layer_backward_f32_workspace_bytes(B, C) bytes, 8-byte aligned (the
+ * components' constants and the workgroups' partials, doubles).
+ */
+gcg_status gcg_bigaus_layer_f32(int64_t B, int64_t C, const float* X, const float* mus,
+                                const float* sigmas_raw, const float* corxy_raw, float* G,
+                                int64_t ldg, gcg_stream_t stream);
+gcg_status gcg_bigaus_layer_backward_f32_workspace_bytes(int64_t B, int64_t C, size_t* bytes);
+gcg_status gcg_bigaus_layer_backward_f32(int64_t B, int64_t C, const float* X, const float* mus,
+                                         const float* sigmas_raw, const float* corxy_raw,
+                                         const float* dG, int64_t lddg,
+                                         const float* scale_dev /*nullable*/, float* dparams,
+                                         void* workspace, size_t workspace_bytes,
+                                         gcg_stream_t stream);
+
+/*
+ * Softmax cross-entropy of wide logits rows against sparse soft targets (reference
+ * loc2lang.py:193-196 on the bag of words of loc2lang.py:253, which it densifies per batch).
+ * logits: M x N float32, row stride ldl >= N, 1 <= N <= 2^24; the columns [N, ldl) are never
+ * read. The target Y is a CSR of y_rows x N (int32 y_indptr / y_indices, float32 y_vals); row i
+ * of the logits is paired with row rows[i] of Y (rows: M device int32, may repeat, any order),
+ * or with row i when rows is NULL (then y_rows >= M). With
+ *     lse = max + log sum_j exp(z_j - max),   T = sum_k y_k   over the entries of the paired row
+ *     loss_rows[i] = sum_k y_k * (lse - z[col_k])
+ *     out[i][j]    = s * (T * softmax(z)_j - y_ij),   s = scale * (*scale_dev or 1 when NULL)
+ * which is the reference's -sum_j y_j log softmax(z)_j and its gradient wherever that is finite
+ * (0 * log 0 does not arise here). An empty target row gives loss 0 and a zero gradient row.
+ * y_indptr == NULL: out = softmax(logits) (predict; loss_rows is not written). out == NULL: the
+ * losses only (evaluation). out (M x N, row stride ldo >= N) may be the logits themselves: every
+ * z[col_k] is read before the row is overwritten.
+ * One workgroup of 256 threads owns a row: (1) one pass over the row with 16-B loads (4-B loads
+ * where the row is not 16-B aligned, same values) in which thread t folds the column quads
+ * t, t + 256, ... in order into a running (max, sum) pair -- per quad its maximum first, one
+ * rescale of the sum, then the four terms in column order -- the lanes' pairs merged by an xor
+ * butterfly (32, 16, .., 1) and the four waves' as ((w0 + w1) + w2) + w3, a merge being
+ * max = max(m1, m2), sum = s1 exp(m1 - max) + s2 exp(m2 - max); (2) the loss gather, thread t
+ * adding the entries t, t + 256, ... of the target row, lanes by the butterfly and waves in
+ * order; (3) a second pass over the row (cache-resident up to a few 10^5 columns) that writes
+ * s T softmax; (4) after a workgroup barrier the same workgroup subtracts s y_k at column col_k.
+ * The order is a fixed function of N: a row's results do not depend on M, the grid or its
+ * position, and two calls agree bit for bit. No atomics.
+ * The rows of Y must be free of duplicate columns: step (4) is a plain read-modify-write, and of
+ * two entries on one column one update would be lost. An entry whose column is outside [0, N) is
+ * skipped, and a row whose rows[i] is outside [0, y_rows) gets a NaN loss and a zero gradient
+ * row; neither is ever used as an index. y_indptr itself (monotone, within the arrays) is the
+ * caller's to validate (gcg_csr_validate). Validates on the host, allocates nothing, returns
+ * GCG_OK without a launch when M == 0.
+ */
+gcg_status gcg_softmax_xent_csr_f32(int64_t M, int64_t N, const float* logits, int64_t ldl,
+                                    int64_t y_rows, const int32_t* y_indptr /*nullable*/,
+                                    const int32_t* y_indices, const float* y_vals,
+                                    const int32_t* rows /*nullable*/, float scale,
+                                    const float* scale_dev /*nullable*/, float* out /*nullable*/,
+                                    int64_t ldo, float* loss_rows, gcg_stream_t stream);
 
 /*
  * CSR transpose on the device (CSR(X^T) for the X^T . dZ1 gradient of
