@@ -3,13 +3,15 @@
 
   k-d-tree regions of the training coordinates (geo.KDTreeClustering)
   -> the regions' means, deviations and correlations (mdn.cluster_params) as the initial Gaussians
+     (--init kmeans: the reference's get_cluster_centers instead, k-means into --ncomp clusters
+     on the device, kmeans.get_cluster_centers)
   -> NNModel_loc2lang.fit on (coordinate, bag of words) pairs
   -> the word distribution over a coordinate grid -> the most local words (local_words).
 
 Three places, each with words of its own and a few that everybody uses; the local words found
 at the end should be the places' own.
 
-    python examples/loc2lang_pipeline.py [--epochs 40]
+    python examples/loc2lang_pipeline.py [--epochs 40] [--init kmeans --ncomp 6]
 """
 from __future__ import annotations
 
@@ -22,7 +24,7 @@ import scipy.sparse as sps
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from graphconvgeo_amd import geo, loc2lang, mdn  # noqa: E402
+from graphconvgeo_amd import geo, kmeans, loc2lang, mdn  # noqa: E402
 
 PLACES = np.array([[40.7, -74.0], [34.0, -118.2], [29.8, -95.4]])
 OWN, COMMON = 10, 10  # words per place, words of everybody
@@ -44,15 +46,23 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument("--epochs", type=int, default=40)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--init", choices=("kdtree", "kmeans"), default="kdtree",
+                    help="where the initial Gaussians come from")
+    ap.add_argument("--ncomp", type=int, default=6, help="components of --init kmeans")
     args = ap.parse_args()
     rng = np.random.default_rng(0)
     np.random.seed(0)
     (Xtr, Ytr), (Xdev, Ydev), (Xte, Yte) = (synthetic(n, rng) for n in (1200, 300, 300))
 
-    tree = geo.KDTreeClustering(bucket_size=200).fit(Xtr, device=args.device)
-    labels, C = tree.clusters.cpu().numpy(), tree.num_clusters
-    mus, sigmas, corxy = mdn.cluster_params(Xtr, labels, C, raw=True)
-    print(f"{C} regions -> {C} Gaussians")
+    if args.init == "kmeans":
+        C = args.ncomp
+        mus, sigmas, corxy = kmeans.get_cluster_centers(Xtr, C, seed=0, device=args.device)
+        print(f"k-means -> {C} Gaussians")
+    else:
+        tree = geo.KDTreeClustering(bucket_size=200).fit(Xtr, device=args.device)
+        labels, C = tree.clusters.cpu().numpy(), tree.num_clusters
+        mus, sigmas, corxy = mdn.cluster_params(Xtr, labels, C, raw=True)
+        print(f"{C} regions -> {C} Gaussians")
 
     clf = loc2lang.NNModel_loc2lang(n_epochs=args.epochs, batch_size=100, hid_size=32,
                                     n_gaus_comp=C, mus=mus, sigmas=sigmas, corxy=corxy,

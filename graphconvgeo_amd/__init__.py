@@ -17,6 +17,8 @@ Product modules (all compute runs in libgcg_spmm.so HIP kernels; no CPU fallback
                "mixture" prediction rule, NNModel_lang2loc (text -> lat/lon) on the GPU
   loc2lang     the location-to-language model (loc2lang.py): the Gaussian layer, softmax
                cross-entropy against sparse soft targets, Adamax, NNModel_loc2lang (lat/lon -> words)
+  kmeans       get_cluster_centers: k-means++ / Lloyd k-means and the per-cluster statistics that
+               start the mixture models' Gaussians, float64 on the GPU
   synth        seeded synthetic graphs / features for the BASELINE configs
 
 `MLP`, `input_convolution`, `NNModel_lang2loc`, `NNModel_lang2locshared`, `NNModel_loc2lang` and

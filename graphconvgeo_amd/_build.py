@@ -17,14 +17,15 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 # SpGEMM, MFMA dense projection + softmax/xent, Philox dropout, the mini-batch MLP's epoch
 # segmentation and W1 step, k-d-tree labels + geolocation metrics, the mixture-density location
 # head with the Gaussian layer of the inverse model, the softmax cross-entropy against sparse
-# soft targets, error/version helpers.
+# soft targets, the k-means initialisation of the Gaussian components, error/version helpers.
 # Compiled in parallel, linked into one shared library.
 SOURCES = [os.path.join(CSRC, f) for f in
            ("spmm.hip", "spmm_bf16.hip", "csr_ops.hip", "graph_build.hip", "spgemm.hip", "dense.hip", "dropout.hip",
-            "minibatch.hip", "geo.hip", "mdn.hip", "softmax_csr.hip", "errors.cpp")]
+            "minibatch.hip", "geo.hip", "kmeans.hip", "mdn.hip", "softmax_csr.hip", "errors.cpp")]
 INTERNAL_HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "spmm_shared.h", "index_kernels.h",
                                                     "gemm_epilogue.inc", "philox.h",
-                                                    "rectify_backward_pass.inc")]
+                                                    "rectify_backward_pass.inc",
+                                                    "segment_kernels.h")]
 HEADER = os.path.join(REPO_DIR, "include", "gcg_spmm.h")
 LIB = os.path.join(PKG_DIR, "libgcg_spmm.so")
 ARCH = os.environ.get("GCG_OFFLOAD_ARCH", "gfx950")

@@ -160,6 +160,18 @@ SIGNATURES = {
     "gcg_nearest_class_f64": (C.c_int, [_i64, _p, _i64, _p, C.c_double, _p, _p, _p]),
     "gcg_geo_eval_f64": (C.c_int, [_i64, _p, C.c_int, _p, _i64, _p, C.c_double, C.c_double, _p,
                                    _p, _p, _p]),
+    # k-means initialisation of the Gaussian components (csrc/kmeans.hip)
+    "gcg_kmeans_centre_tile": (C.c_int32, []),
+    "gcg_kmeans_assign_f64_workspace_bytes": (C.c_int, [_i64, _psz]),
+    "gcg_kmeans_assign_f64": (C.c_int, [_i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, C.c_size_t,
+                                        _p]),
+    "gcg_kmeans_update_f64_workspace_bytes": (C.c_int, [_i64, _i64, _psz]),
+    "gcg_kmeans_update_f64": (C.c_int, [_i64, _p, _p, _i64, _p, _p, _p, _p, _p, C.c_size_t, _p]),
+    "gcg_kmeans_pp_f64_workspace_bytes": (C.c_int, [_i64, _psz]),
+    "gcg_kmeans_pp_f64": (C.c_int, [_i64, _p, _i64, _p, _p, _p, _p, C.c_size_t, _p]),
+    "gcg_cluster_stats_f64_workspace_bytes": (C.c_int, [_i64, _i64, _psz]),
+    "gcg_cluster_stats_f64": (C.c_int, [_i64, _p, _p, _i64, C.c_int, _p, _p, _p, _p, _p, _p,
+                                        C.c_size_t, _p]),
     "gcg_spgemm_ex": (C.c_int, [_i64, _i64, _i64, _i64, _p, _p, _p, C.c_int, _i64, _p, _p, _p,
                                 C.c_int, _i64, _p, _p, _p, _p, C.c_int32, _i64, _p]),
 }

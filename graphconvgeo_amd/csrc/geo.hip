@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "segment_kernels.h"
 
 using namespace gcg;
 
@@ -34,13 +35,6 @@ struct DevMem {
   }
   template <typename T> T* as() const { return static_cast<T*>(p); }
 };
-
-__device__ __forceinline__ int64_t grid_start() {
-  return static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-}
-__device__ __forceinline__ int64_t grid_stride() {
-  return static_cast<int64_t>(gridDim.x) * blockDim.x;
-}
 
 // locs (N x 2 row-major) -> vals[0..N) latitudes, vals[N..2N) longitudes; ids = 0..N-1;
 // a non-finite coordinate raises *status.
@@ -226,16 +220,6 @@ __global__ void gather_labels_kernel(int64_t N, int64_t C, const int32_t* __rest
       l = 0;
     }
     keys[p] = l;
-  }
-}
-
-// ptr[c] = the first position of class c in the sorted labels (ptr[C] = N).
-__global__ void class_ptr_kernel(int64_t N, int64_t C, const int32_t* __restrict__ sorted,
-                                 int32_t* __restrict__ ptr) {
-  for (int64_t p = grid_start(); p <= N; p += grid_stride()) {
-    const int64_t prev = p == 0 ? -1 : sorted[p - 1];
-    const int64_t cur = p == N ? C : sorted[p];
-    for (int64_t c = prev + 1; c <= cur; ++c) ptr[c] = static_cast<int32_t>(p);
   }
 }
 

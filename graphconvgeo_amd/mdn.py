@@ -309,7 +309,8 @@ def cluster_params(latlon, labels, n_cluster: int, raw: bool = True):
     Deviations: the labels come from the caller (geo.KDTreeClustering: deterministic, on the
     device) where the reference runs MiniBatchKMeans, so mus is the members' mean, not a k-means
     centre; the reference leaves the correlation undefined for a single member, here it is 0.
-    No hot path: NumPy on the host."""
+    No hot path: NumPy on the host. kmeans.get_cluster_centers is the reference's whole
+    function, k-means and these statistics on the device."""
     latlon = np.asarray(latlon, dtype=np.float64)
     labels = np.asarray(labels)
     n = int(n_cluster)

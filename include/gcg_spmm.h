@@ -1031,6 +1031,89 @@ gcg_status gcg_geo_eval_f64(int64_t M, const void* pred, int pred_is_int64, cons
                             double threshold_km, double* distance, int64_t* count_dev,
                             int32_t* status_dev, gcg_stream_t stream);
 
+/*
+ * k-means initialisation of the Gaussian components (csrc/kmeans.hip): get_cluster_centers of
+ * lang2loc.py:473-478, lang2loc_mdnshared.py:127-185 and loc2lang.py:326-371 as full Lloyd
+ * k-means (the reference runs MiniBatchKMeans on the host). Coordinates as above: N x 2 float64,
+ * N <= 2^30 - 2; labels, indices and counts are int32; the metric is Euclidean on raw degrees,
+ * as the reference's. Every squared distance is
+ *     d = (x0 - c0) * (x0 - c0) + (x1 - c1) * (x1 - c1)
+ * with each operation rounded once, in that order (no fused multiply-add), and strict < keeps
+ * the lowest index on a tie. No result depends on the launch grid or on timing; there are no
+ * floating-point atomics. Scratch is the caller's: every *_workspace_bytes function gives the
+ * size for (N, C), the workspace is 256-B aligned, and no entry synchronizes the stream.
+ * *status_dev (device int32, reset by every call) reports data errors.
+ *
+ * gcg_kmeans_assign_f64: labels[i] = the nearest centre of point i; dist2[i] (nullable) = that
+ * squared distance. One kernel: 4 points per thread (point g * 1024 + t + 256 p for thread t of
+ * workgroup g), the centres staged through LDS in tiles of gcg_kmeans_centre_tile() = 1024.
+ *   changed_dev (nullable)  1 when prev_labels is given and some label differs from it, else 0
+ *   inertia_dev (nullable)  the sum of the minima: a thread adds its points in ascending p, a
+ *                 workgroup its threads in the tree s[t] += s[t + h], h = 128 .. 1, and one
+ *                 workgroup adds the per-workgroup partials the same way (thread t takes
+ *                 partials t, t + 256, ... in ascending order). Needs the workspace.
+ *   status_dev    1 for a non-finite coordinate in locs
+ * A NaN centre is never the nearest. N = 0 is a no-op (inertia 0); C >= 1 unless N = 0.
+ */
+int32_t gcg_kmeans_centre_tile(void);
+gcg_status gcg_kmeans_assign_f64_workspace_bytes(int64_t N, size_t* bytes);
+gcg_status gcg_kmeans_assign_f64(int64_t N, const double* locs, int64_t C, const double* centers,
+                                 const int32_t* prev_labels /*nullable*/, int32_t* labels,
+                                 double* dist2 /*nullable*/, double* inertia_dev /*nullable*/,
+                                 int32_t* changed_dev /*nullable*/, int32_t* status_dev,
+                                 void* workspace, size_t workspace_bytes, gcg_stream_t stream);
+
+/*
+ * centers[c] = the float64 sum of the members of cluster c divided by counts[c]; an empty
+ * cluster keeps prev_centers[c] and gets count 0 (centers may be prev_centers). Reduction order:
+ * a stable radix sort of (label, index) groups the members by cluster in ascending index; one
+ * workgroup of 256 threads per cluster, thread t adding members t, t + 256, ... of the segment
+ * in that order, then the tree s[t] += s[t + h], h = 128 .. 1. The grid only decides which
+ * workgroup takes which cluster, so the result is bitwise the same from call to call.
+ * *status_dev = 1 for a label outside [0, C) (it counts as cluster 0).
+ */
+gcg_status gcg_kmeans_update_f64_workspace_bytes(int64_t N, int64_t C, size_t* bytes);
+gcg_status gcg_kmeans_update_f64(int64_t N, const double* locs, const int32_t* labels, int64_t C,
+                                 const double* prev_centers, double* centers, int32_t* counts,
+                                 int32_t* status_dev, void* workspace, size_t workspace_bytes,
+                                 gcg_stream_t stream);
+
+/*
+ * k-means++ seeding, one trial per centre, as a pure function of the uniform draws u_dev[C]
+ * (device float64 in [0, 1)): indices[0] = floor(u[0] * N); for k >= 1, D2[i] = the minimum over
+ * the chosen centres of the squared distance above, S = the inclusive prefix sum of D2 in index
+ * order, and indices[k] = the first i with S_i > u[k] * S_{N-1}, clamped to the last i with
+ * D2[i] > 0 -- a point at distance 0 from a chosen centre is never picked. S is summed in fixed
+ * levels, each in ascending order: the 8 consecutive points of a thread, the 256 threads of a
+ * workgroup (2048 points), the workgroups of a chunk of ceil(nb / 256), the 256 chunks. The C
+ * rounds are two launches each, sequential on the stream; the chosen index stays on the device.
+ *   status_dev  1: S_{N-1} = 0 before all C were chosen (fewer distinct points than C);
+ *               2: a non-finite coordinate; 3: a draw outside [0, 1). indices are then undefined
+ *               (but inside [0, N)).
+ * 1 <= C <= N.
+ */
+gcg_status gcg_kmeans_pp_f64_workspace_bytes(int64_t N, size_t* bytes);
+gcg_status gcg_kmeans_pp_f64(int64_t N, const double* locs, int64_t C, const double* u_dev,
+                             int32_t* indices, int32_t* status_dev, void* workspace,
+                             size_t workspace_bytes, gcg_stream_t stream);
+
+/*
+ * The per-cluster statistics of get_cluster_centers for any labels[N] in [0, C): counts
+ * (nullable), means (C x 2), the ddof-1 standard deviations sigmas (C x 2) and the correlation
+ * corxys (C). Members are grouped and summed as in gcg_kmeans_update_f64, in two passes: the
+ * deviations from the segment's first member f give the mean f + sum / n, the deviations from
+ * that mean the (co)variances -- identical points have variance exactly 0. A single member, a
+ * zero variance, a NaN or an empty cluster give (1, 1, 0); an empty cluster leaves means[c] as
+ * passed in. raw = 1 stores s + log1p(-exp(-s)) and c / (1 - |c|), the inverses of the models'
+ * softplus and softsign. *status_dev = 1 for a label outside [0, C).
+ */
+gcg_status gcg_cluster_stats_f64_workspace_bytes(int64_t N, int64_t C, size_t* bytes);
+gcg_status gcg_cluster_stats_f64(int64_t N, const double* locs, const int32_t* labels, int64_t C,
+                                 int raw, double* means /*in, out*/, double* sigmas,
+                                 double* corxys, int32_t* counts /*nullable*/,
+                                 int32_t* status_dev, void* workspace, size_t workspace_bytes,
+                                 gcg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
