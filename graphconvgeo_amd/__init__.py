@@ -9,6 +9,8 @@ Product modules (all compute runs in libgcg_spmm.so HIP kernels; no CPU fallback
   dist_train   the row-partitioned GCN training step (backward through H's symmetry)
   graph        H = D^-1/2 (A+I) D^-1/2 construction, host (scipy) and device (HIP)
   mentions     mention-graph parsing (host) and projection (HIP), data.py:226-375
+  training     what the trainers share: the optimiser base, the epoch loop and its improvement
+               rules, the host half of a mini-batch epoch
   mlpconv      MLPCONV trainer (mlpconv.py:121-352) on the GPU
   mlp          MLP mini-batch trainer (mlp.py:96-311) on the GPU, input_convolution (H * X)
   geo          k-d-tree region labels (kdtree.py), class medians, haversine, nearest class and
@@ -37,7 +39,8 @@ __version__ = "0.1.0"
 _os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "8")
 
 __all__ = ["sparse", "ops", "layers", "dense", "distributed", "dist_train", "graph", "mentions",
-           "mlpconv", "mlp", "geo", "mdn", "loc2lang", "synth", "MLP", "input_convolution",
+           "training", "mlpconv", "mlp", "geo", "mdn", "loc2lang", "synth", "MLP",
+           "input_convolution",
            "NNModel_lang2loc", "NNModel_lang2locshared", "NNModel_loc2lang", "DeviceCSR"]
 
 _LAZY = {"MLP": "mlp", "input_convolution": "mlp", "NNModel_lang2loc": "mdn",

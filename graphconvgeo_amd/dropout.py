@@ -34,7 +34,7 @@ import torch.nn as nn
 
 from . import sparse as gs
 from ._native import call
-from .sparse import _ptr, _stream_handle
+from .sparse import _ld, _ptr, _stream_handle
 
 _M0, _M1 = 0xD2511F53, 0xCD9E8D57
 _W0, _W1 = 0x9E3779B9, 0xBB67AE85
@@ -167,10 +167,6 @@ def make_spec(stream: Optional[DropoutStream], p: float, rescale: bool = True,
 # ---------------------------------------------------------------------------------------
 # the three entry points
 # ---------------------------------------------------------------------------------------
-def _ld(t: torch.Tensor) -> int:
-    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
-
-
 def _check_2d(t: torch.Tensor, name: str):
     gs._require_cuda(t, name)
     if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):

@@ -29,25 +29,21 @@ from typing import Optional
 import numpy as np
 import scipy.sparse as sps
 import torch
-from torch.autograd.graph import increment_version
 
 from . import dense
 from . import sparse as gs
 from ._native import call
 from .layers import _as_tensor, _glorot_uniform
 from .mdn import MAX_COMPONENTS, _check_components, split_dparams
-from .mlp import n_batches
-from .sparse import _ptr, _stream_handle
+from .sparse import _ld, _ptr, _stream_handle
+from .training import (LasagneOptimizer, MiniBatchTrainer, lower_loss_by_margin, n_batches,
+                       run_epochs)
 
 log = logging.getLogger(__name__)
 
 MAX_COLS = 1 << 24          # gcg_softmax_xent_csr_f32's widest row
 MAX_HIDDEN = 1024           # the rectify backward's one-pass kernel (sparse.relu_backward)
 EVAL_CHUNK_BYTES = 1 << 30  # a chunk's logits stay under this in evaluation and predict
-
-
-def _ld(t: torch.Tensor) -> int:
-    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
 
 
 # -- the Gaussian layer ---------------------------------------------------------------------
@@ -320,61 +316,18 @@ def softmax_wide(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> to
 
 
 # -- Adamax -------------------------------------------------------------------------------------
-class LasagneAdamax:
+class LasagneAdamax(LasagneOptimizer):
     """lasagne.updates.adamax: t += 1; a_t = lr/(1-b1^t); m = b1*m + (1-b1)*g;
     u = max(b2*u, |g|); p -= a_t*m/(u+eps). mlpconv.LasagneAdam's interface."""
 
-    def __init__(self, params, lr=2e-3, beta1=0.9, beta2=0.999, epsilon=1e-8):
-        self.params = list(params)
-        self.lr, self.beta1, self.beta2, self.eps = lr, beta1, beta2, epsilon
-        self.t = 0
-        self.m = [torch.zeros_like(p) for p in self.params]
-        self.u = [torch.zeros_like(p) for p in self.params]
-        # a_t lives on the device, as LasagneAdam's
-        self.a_t = torch.zeros((), dtype=torch.float32, device=self.params[0].device)
+    entry, second, lr = "gcg_adamax_step_f32", "u", 2e-3
 
-    def prepare(self):
-        """Host half of a step: t += 1 and the bias-corrected step size (Python double, rounded
-        once to float32)."""
-        self.t += 1
-        self.a_t.fill_(self.lr / (1 - self.beta1 ** self.t))
-
-    @torch.no_grad()
-    def apply(self):
-        """Device half of a step: one fused launch per parameter (gcg_adamax_step_f32)."""
-        for p, m, u in zip(self.params, self.m, self.u):
-            g = p.grad.contiguous()
-            if not p.is_contiguous():
-                raise ValueError("LasagneAdamax needs contiguous parameters")
-            with torch.cuda.device(p.device):
-                call("gcg_adamax_step_f32", p.numel(), _ptr(p), _ptr(g), _ptr(m), _ptr(u),
-                     _ptr(self.a_t), self.beta1, self.beta2, self.eps, _stream_handle(p.device))
-            # an in-place write through a raw pointer: bump the version counters as a torch
-            # in-place op would, so the padded weight copies (dense._WeightCache) follow
-            increment_version(p)
-            increment_version(m)
-            increment_version(u)
-
-    def step(self):
-        self.prepare()
-        self.apply()
-
-    def state(self):
-        return {"t": self.t, "m": [x.clone() for x in self.m], "u": [x.clone() for x in self.u]}
-
-    @torch.no_grad()
-    def load_state(self, st):
-        self.t = st["t"]
-        for dst, src in zip(self.m + self.u, st["m"] + st["u"]):
-            dst.copy_(src)
-
-    def zero_grad(self):
-        for p in self.params:
-            p.grad = None
+    def step_size(self, t):
+        return self.lr / (1 - self.beta1 ** t)
 
 
 # -- the model ------------------------------------------------------------------------------
-class NNModel_loc2lang:
+class NNModel_loc2lang(MiniBatchTrainer):
     """loc2lang.NNModel (loc2lang.py:118-292) with every product, the Gaussian layer, the loss
     and the update on the GPU.
 
@@ -467,9 +420,6 @@ class NNModel_loc2lang:
     def names(self):
         return ["mus", "sigmas", "corxy"] + (["Wh", "bh"] if self.hid_size else []) + ["Wo", "bo"]
 
-    def _param(self, x, shape):
-        return torch.nn.Parameter(_as_tensor(x, shape, self.device), requires_grad=False)
-
     def _build(self, V: int):
         if not 1 <= V <= MAX_COLS:
             raise ValueError(f"output_size must be in [1, {MAX_COLS}]")
@@ -534,19 +484,6 @@ class NNModel_loc2lang:
         return float(np.cumsum(losses.cpu().numpy().astype(np.float64))[-1] / n)
 
     # -- training -----------------------------------------------------------------------
-    def _prepare_epoch(self, order) -> None:
-        """Host half of an epoch: the order checked to be a permutation, cut into whole batches
-        and uploaded; its coordinates gathered once."""
-        n, B = self._x_train.shape[0], self.batch_size
-        order = np.asarray(order)
-        if order.ndim != 1 or order.size != n or \
-                not np.array_equal(np.sort(order), np.arange(n)):
-            raise ValueError(f"an epoch's order must be a permutation of the {n} training rows")
-        self._n_batches = n_batches(n, B)
-        perm = np.ascontiguousarray(order[:self._n_batches * B], dtype=np.int32)
-        self._perm = torch.from_numpy(perm).to(self.device)
-        self._x_epoch = self._x_train.index_select(0, self._perm.to(torch.int64))
-
     @torch.no_grad()
     def _step(self, x: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
         """One batch: the loss (device scalar) and the gradients of every parameter, then the
@@ -573,23 +510,18 @@ class NNModel_loc2lang:
 
     @torch.no_grad()
     def _run_batches(self) -> torch.Tensor:
-        """Device half of an epoch: every batch's step, no host synchronisation. Returns the
-        mean of the batch losses as a device scalar."""
+        """Device half of an epoch (the host half: MiniBatchTrainer._prepare_epoch, which
+        gathers the epoch's coordinates): every batch's step, no host synchronisation. Returns
+        the mean of the batch losses as a device scalar."""
         B = self.batch_size
         total = torch.zeros((), dtype=torch.float32, device=self.device)
         self.batch_losses = []
         for b in range(self._n_batches):
-            loss = self._step(self._x_epoch[b * B:(b + 1) * B], self._perm[b * B:(b + 1) * B])
+            loss = self._step(self._epoch_data[b * B:(b + 1) * B],
+                              self._perm[b * B:(b + 1) * B])
             self.batch_losses.append(loss)
             total += loss
         return total / self._n_batches
-
-    def _train_epoch(self, order=None) -> torch.Tensor:
-        if order is None:  # loc2lang.py:219-221, numpy's global stream
-            order = np.arange(self._x_train.shape[0])
-            np.random.shuffle(order)
-        self._prepare_epoch(order)
-        return self._run_batches()
 
     def _split(self, X, Y, name: str):
         x = self._to_coords(X, name)
@@ -604,7 +536,8 @@ class NNModel_loc2lang:
         words, scipy sparse or dense [n, V], uploaded once as CSR. Returns
         (perplexity_test, perplexity_dev). epoch_orders (tests, measurement): one permutation of
         the training rows per epoch instead of the np.random.shuffle draws."""
-        self._x_train, self._y_train = self._split(X_train, Y_train, "train")
+        self._train_data, self._y_train = self._split(X_train, Y_train, "train")
+        self._n_train = self._train_data.shape[0]
         x_dev, y_dev = self._split(X_dev, Y_dev, "dev")
         x_test, y_test = self._split(X_test, Y_test, "test")
         V = self._y_train.n_cols
@@ -614,35 +547,21 @@ class NNModel_loc2lang:
             self._build(V)
         elif self.output_size != V:
             raise ValueError(f"Y_train has {V} columns, output_size says {self.output_size}")
-        n_batches(self._x_train.shape[0], self.batch_size)  # n < B raises
+        n_batches(self._n_train, self.batch_size)  # n < B raises
         if x_dev.shape[0] == 0 or x_test.shape[0] == 0:
             raise ValueError("the dev and test splits need at least one row")
         log.info("training with %d n_epochs and %d batch_size", self.n_epochs, self.batch_size)
         self.history, self.epoch_batch_losses = [], []
-        best_params, best_val_loss, n_down = None, float("inf"), 0
-        for n in range(self.n_epochs):
-            order = None if epoch_orders is None else epoch_orders[n]
-            l_train = self._train_epoch(order)
-            l_val = self._evaluate(x_dev, y_dev)
-            l_train = float(l_train)
-            self.epoch_batch_losses.append(torch.stack(self.batch_losses).cpu().numpy())
-            stop = False
-            if l_val < best_val_loss and (best_val_loss - l_val) > (0.0001 * l_val):
-                best_val_loss, n_down = l_val, 0
-                best_params = [p.detach().clone() for p in self.params]
-            else:
-                n_down += 1
-                stop = n_down > self.early_stopping_max_down
-            self.history.append({"epoch": n, "train_loss": l_train, "val_loss": l_val})
-            if stop:
-                log.info("validation results went down. early stopping ...")
-                break
-            log.info("iter %d, train loss %f, dev loss %f, best dev loss %f, num_down %d", n,
-                     l_train, l_val, best_val_loss, n_down)
+        best, best_params = run_epochs(
+            lambda n: (self._train_epoch(None if epoch_orders is None else epoch_orders[n]),),
+            lambda: (self._evaluate(x_dev, y_dev),), self.params, self.history, self.n_epochs,
+            lower_loss_by_margin, self.early_stopping_max_down,
+            after_epoch=lambda n: self.epoch_batch_losses.append(
+                torch.stack(self.batch_losses).cpu().numpy()))
+        self.best_val_loss = best[0]
         self.last_params = [p.detach().cpu().numpy() for p in self.params]
         if best_params is not None:  # None: no epoch qualified; keep the last parameters
             self.set_params(best_params)
-        self.best_val_loss = best_val_loss
         l_test = self._evaluate(x_test, y_test)
         l_dev = self._evaluate(x_dev, y_dev)
         self.test_loss, self.dev_loss = l_test, l_dev

@@ -35,26 +35,22 @@ import logging
 from typing import Optional
 
 import numpy as np
-import scipy.sparse as sps
 import torch
 
 from . import dense, geo
 from . import sparse as gs
-from ._native import GCG_ACT_NONE, call
+from ._native import call
 from .dropout import DropoutStream, draw_seed, make_spec
-from .layers import _as_tensor, _glorot_uniform, _upload_cached
-from .mlp import BatchSegments, n_batches, plan_epoch, w1_step
+from .layers import _as_tensor, _glorot_uniform
+from .mlp import BatchSegments, plan_segmented_epoch, w1_step
 from .mlpconv import LasagneAdam
-from .sparse import _ptr, _stream_handle
+from .sparse import _ld, _ptr, _stream_handle
+from .training import MiniBatchTrainer, lower_loss, n_batches, restore, run_epochs
 
 log = logging.getLogger(__name__)
 
 MAX_COMPONENTS = 1024
 METHODS = {"mixture": 0, "pi": 1}
-
-
-def _ld(t: torch.Tensor) -> int:
-    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
 
 
 def _check_output(O: torch.Tensor, n_comp: int) -> torch.Tensor:
@@ -353,18 +349,20 @@ def geo_eval_latlon(pred_latlon, locs, earth_radius_km: float = geo.EARTH_RADIUS
     return geo.geo_eval(classes, locs, pred_latlon, earth_radius_km, threshold_km, device=device)
 
 
-class _MdnTrainer:
+class _MdnTrainer(MiniBatchTrainer):
     """What NNModel_lang2loc and NNModel_lang2locshared share: the constructor arguments of the
-    reference, the sparse input and the hidden layer tanh(X.W1 + b1), the host half of an epoch,
-    the batch loop (one step per batch, W1 updated in one pass over the batch's segments), the
-    dev loss over whole batches, and fit with its strict-`<` model selection, early stopping and
-    restore. A model states its head: _build (its parameters and optimiser), _head_backward (a
-    batch's loss with the gradients of everything but W1 and b1), _loss (the deterministic loss
-    of a raw output) and _penalty_coefs / _penalty."""
+    reference, the hidden layer tanh(X.W1 + b1), the batch loop (one step per batch, W1 updated
+    in one pass over the batch's segments), the dev loss over whole batches, and fit: the shared
+    loop (training.run_epochs) with the strict-`<` rule, early stopping and restore. The sparse
+    inputs and the host half of an epoch are training.MiniBatchTrainer's. A model states its
+    head: _build (its parameters and optimiser), _head_backward (a batch's loss with the
+    gradients of everything but W1 and b1), _loss (the deterministic loss of a raw output) and
+    _penalty_coefs / _penalty."""
 
     n_init_parameters = 4
     init_names = "[W1, b1, W2, b2]"
     nan_stops = False  # lang2loc_mdnshared.py:627-629: a NaN dev loss ends fit with None
+    _plan_epoch = plan_segmented_epoch
 
     def __init__(self, n_epochs=10, batch_size=1000, regul_coef=1e-6, input_size=None,
                  output_size=None, hid_size=100, drop_out=False, dropout_coef=0.5,
@@ -431,9 +429,6 @@ class _MdnTrainer:
         self._proj = dense.Projection()
         return None if init is None else init[4:]
 
-    def _param(self, x, shape):
-        return torch.nn.Parameter(_as_tensor(x, shape, self.device), requires_grad=False)
-
     def _make_optimizer(self):
         """Adam at lr 1e-3 on every parameter; W1's state lives beside it (updated inside the
         W1 step kernel)."""
@@ -442,31 +437,12 @@ class _MdnTrainer:
         self.m1 = torch.zeros_like(self.W1)
         self.v1 = torch.zeros_like(self.W1)
 
-    def _input(self, X) -> gs.DeviceCSR:
-        if isinstance(X, gs.DeviceCSR):
-            Xd = X
-        elif sps.issparse(X):
-            Xd = _upload_cached(self._inputs, X.tocsr() if X.format != "csr" else X, self.device)
-        else:
-            raise ValueError("Input for this layer must be sparse")
-        if hasattr(self, "in_size") and Xd.n_cols != self.in_size:
-            raise ValueError(f"X has {Xd.n_cols} columns, the model {self.in_size}")
-        return Xd
-
-    def _hidden(self, X: gs.DeviceCSR, vals: torch.Tensor, rows: Optional[torch.Tensor],
-                n_out: int) -> torch.Tensor:
-        """tanh(X[rows].W1 + b1) with X's values read from `vals`: the plan-less SpMM (one wave
-        per output row, no activation in its epilogue), then tanh in place. rows: int32 device
-        row ids, range-checked by the caller; None: the first n_out rows are all of X."""
-        K, dev = self.hid_size, self.device
-        h = gs.empty_dense(n_out, K, dev)
-        if n_out == 0:
-            return h
-        with torch.cuda.device(dev):
-            call("gcg_spmm_csr_f32_gate", X.n_rows, X.n_cols, X.nnz, _ptr(X.indptr),
-                 _ptr(X.indices), _ptr(vals), _ptr(self.W1), K, K, _ptr(h), _ld(h),
-                 _ptr(self.b1), GCG_ACT_NONE, _ptr(rows), n_out, None, 0, _stream_handle(dev))
-        return h.tanh_()
+    def _hidden(self, X: gs.DeviceCSR, vals: torch.Tensor, rows: Optional[torch.Tensor]
+                ) -> torch.Tensor:
+        """tanh(X[rows].W1 + b1) with X's values read from `vals`: the plan-less SpMM (no
+        activation in its epilogue), then tanh in place. rows: int32 device row ids,
+        range-checked by the caller; None: every row of X."""
+        return gs.spmm_rows(X, self.W1, self.b1, rows, vals=vals).tanh_()
 
     @torch.no_grad()
     def _output(self, Xd: gs.DeviceCSR, n_rows: Optional[int] = None) -> torch.Tensor:
@@ -475,7 +451,7 @@ class _MdnTrainer:
         rows = None
         if n != Xd.n_rows:
             rows = torch.arange(n, dtype=torch.int32, device=self.device)
-        h = self._hidden(Xd, Xd.data, rows, n)
+        h = self._hidden(Xd, Xd.data, rows)
         return self._proj.matmul(h, self.W2.detach(), self.b2.detach())
 
     @torch.no_grad()
@@ -495,22 +471,10 @@ class _MdnTrainer:
             raise ValueError(f"{name} must have shape ({n}, 2) [lat, lon], got {Y.shape}")
         return torch.from_numpy(np.ascontiguousarray(Y, dtype=np.float32)).to(self.device)
 
-    def _prepare_epoch(self, order) -> None:
-        """Host half of an epoch: the order checked to be a permutation, cut into whole batches
-        and uploaded; its targets gathered once; the runs each segmentation call takes."""
-        n = self.Xd.n_rows
-        order = np.asarray(order)
-        if order.ndim != 1 or order.size != n or \
-                not np.array_equal(np.sort(order), np.arange(n)):
-            # a row in two batches would also share one slot of the dropped values
-            raise ValueError(f"an epoch's order must be a permutation of the {n} training rows")
-        perm, self._runs, self._n_batches = plan_epoch(order, self._indptr_host, self.batch_size)
-        self._perm = torch.from_numpy(perm.astype(np.int32)).to(self.device)
-        self._y_epoch = self._y_train.index_select(0, self._perm.to(torch.int64))
-
     @torch.no_grad()
     def _run_batches(self) -> torch.Tensor:
-        """Device half of an epoch: every batch's step, no host synchronisation. Returns the
+        """Device half of an epoch (the host half: MiniBatchTrainer._prepare_epoch, which
+        gathers the epoch's targets): every batch's step, no host synchronisation. Returns the
         mean of the batch losses (penalty included) as a device scalar."""
         B, dev = self.batch_size, self.device
         X, opt = self.Xd, self.optimizer
@@ -522,8 +486,8 @@ class _MdnTrainer:
             vals = X.data if self._drop is None else self._vals_drop
             for b in range(first, stop):
                 rows = self._perm[b * B:(b + 1) * B]
-                y = self._y_epoch[b * B:(b + 1) * B]
-                h = self._hidden(X, vals, rows, B)
+                y = self._epoch_data[b * B:(b + 1) * B]
+                h = self._hidden(X, vals, rows)
                 opt.zero_grad()
                 h.requires_grad_(True)
                 nll = self._head_backward(h, y)
@@ -538,71 +502,37 @@ class _MdnTrainer:
                 opt.apply()
         return total / self._n_batches
 
-    def _train_epoch(self, order=None) -> torch.Tensor:
-        if order is None:  # lang2loc.py:398-400 (mlp.iterate_minibatch_indices' draw), numpy's
-            order = np.arange(self.Xd.n_rows)  # global stream
-            np.random.shuffle(order)
-        self._prepare_epoch(order)
-        return self._run_batches()
-
     @torch.no_grad()
     def fit(self, X_train, Y_train, X_dev, Y_dev, *ignored, epoch_orders=None):
         """lang2loc.py:408-455. The reference's six further arguments (X_test, Y_test, U_train,
         U_dev, U_test, userLocation) are accepted and ignored, as fit ignores them there.
         epoch_orders (tests, measurement): one permutation of the training rows per epoch
         instead of the np.random.shuffle draws."""
-        for X in (X_train, X_dev):
-            if not (isinstance(X, gs.DeviceCSR) or sps.issparse(X)):
-                raise ValueError("Input for this layer must be sparse")
-        in_size = X_train.shape[1]
+        in_size = self._check_inputs(X_train, X_dev)
         if self.input_size is not None and int(self.input_size) != in_size:
             raise ValueError(f"X_train has {in_size} columns, input_size says {self.input_size}")
-        if X_dev.shape[1] != in_size:
-            raise ValueError("X_train and X_dev differ in width")
-        n_batches(X_train.shape[0], self.batch_size)  # n < B raises
         if X_dev.shape[0] < self.batch_size:
             raise ValueError(f"{X_dev.shape[0]} dev rows are fewer than one batch of "
                              f"{self.batch_size}: the dev loss is a mean over whole batches")
-        self._y_train = self._coords(Y_train, X_train.shape[0], "Y_train")
+        self._train_data = self._coords(Y_train, X_train.shape[0], "Y_train")
         y_dev = self._coords(Y_dev, X_dev.shape[0], "Y_dev")
-        self.Xd = X_train if isinstance(X_train, gs.DeviceCSR) else \
-            gs.DeviceCSR.from_scipy(X_train, self.device)
-        self.Xdev = X_dev if isinstance(X_dev, gs.DeviceCSR) else \
-            gs.DeviceCSR.from_scipy(X_dev, self.device)
-        self._indptr_host = (np.asarray(X_train.indptr) if sps.issparse(X_train) and
-                             X_train.format == "csr" else self.Xd.indptr.cpu().numpy()
-                             ).astype(np.int64)
+        self._upload_inputs(X_train, X_dev)
         self._build(in_size)
         # X's values behind the mask: every batch's rows are rewritten by its segmentation call
         self._vals_drop = torch.zeros_like(self.Xd.data) if self._drop is not None else None
         log.info("training with %d n_epochs and %d batch_size", self.n_epochs, self.batch_size)
         self.history = []
-        best_params, best_val_loss, n_down = None, float("inf"), 0
-        for n in range(self.n_epochs):
-            order = None if epoch_orders is None else epoch_orders[n]
-            l_train = self._train_epoch(order)
-            l_val = self._evaluate(self.Xdev, y_dev)
-            l_train, l_val = float(l_train), float(l_val)
-            if self.nan_stops and np.isnan(l_val):
-                self.nan = True
-                return None
-            stop = False
-            if l_val < best_val_loss:
-                best_val_loss, n_down = l_val, 0
-                best_params = [p.detach().clone() for p in self.params]
-            else:
-                n_down += 1
-                stop = n_down > self.early_stopping_max_down
-            self.history.append({"epoch": n, "train_loss": l_train, "val_loss": l_val})
-            if stop:
-                log.info("validation results went down. early stopping ...")
-                break
-            log.info("iter %d, train loss %f, dev loss %f, best dev loss %f, num_down %d", n,
-                     l_train, l_val, best_val_loss, n_down)
-        if best_params is not None:  # None: no epoch gave a finite improvement; keep the last
-            for p, b in zip(self.params, best_params):
-                p.copy_(b)
-        self.best_val_loss = best_val_loss
+        out = run_epochs(
+            lambda n: (self._train_epoch(None if epoch_orders is None else epoch_orders[n]),),
+            lambda: (self._evaluate(self.Xdev, y_dev),), self.params, self.history,
+            self.n_epochs, lower_loss, self.early_stopping_max_down,
+            abort=np.isnan if self.nan_stops else None)
+        if out is None:
+            self.nan = True
+            return None
+        best, best_params = out
+        self.best_val_loss = best[0]
+        restore(self.params, best_params)  # None: no epoch gave a finite improvement; keep the last
         return self
 
     def get_params(self):

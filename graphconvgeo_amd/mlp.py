@@ -38,10 +38,11 @@ from torch.autograd.graph import increment_version
 
 from . import dense
 from . import sparse as gs
-from ._native import GCG_ACT_NONE, GCG_ACT_RELU, call
-from .layers import _as_device_csr, _as_tensor, _glorot_uniform, _upload_cached
+from ._native import call
+from .layers import _as_device_csr, _glorot_uniform
 from .mlpconv import LasagneAdam
-from .sparse import _ptr, _stream_handle
+from .sparse import _ld, _ptr, _stream_handle
+from .training import MiniBatchTrainer, higher_accuracy, n_batches, restore, run_epochs
 
 log = logging.getLogger(__name__)
 
@@ -59,14 +60,6 @@ def iterate_minibatch_indices(n: int, batchsize: int, shuffle: bool = True):
     if shuffle:
         np.random.shuffle(order)
     return [order[s:s + batchsize] for s in range(0, n - batchsize + 1, batchsize)]
-
-
-def n_batches(n: int, batchsize: int) -> int:
-    if batchsize <= 0:
-        raise ValueError("batch_size must be positive")
-    if n < batchsize:
-        raise ValueError(f"{n} training rows are fewer than one batch of {batchsize}")
-    return (n - batchsize) // batchsize + 1
 
 
 def output_size(Y_train) -> int:
@@ -120,6 +113,13 @@ def plan_epoch(order, indptr_host: np.ndarray, batch: int):
         acc += int(per_batch[b])
     runs.append((start, nb, acc))
     return perm, runs, nb
+
+
+def plan_segmented_epoch(self, order) -> np.ndarray:
+    """MiniBatchTrainer._plan_epoch of the sparse-input trainers: plan_epoch's cut, kept on the
+    host too (`_perm_host`, which tools/bench_mlp.py reads), and its runs (`_runs`)."""
+    self._perm_host, self._runs, _ = plan_epoch(order, self._indptr_host, self.batch_size)
+    return self._perm_host
 
 
 class BatchSegments:
@@ -191,9 +191,8 @@ def w1_step(W: torch.Tensor, m: torch.Tensor, v: torch.Tensor, G: torch.Tensor,
         raise ValueError(f"G must be float32 [{seg.batch}, {K}] with unit column stride")
     if not 0 <= b < seg.n_batches:
         raise IndexError("batch index out of range")
-    ldg = G.stride(0) if seg.batch > 1 else max(K, 1)
     with torch.cuda.device(W.device):
-        call("gcg_minibatch_w1_step_f32", F, K, _ptr(W), _ptr(m), _ptr(v), _ptr(G), ldg,
+        call("gcg_minibatch_w1_step_f32", F, K, _ptr(W), _ptr(m), _ptr(v), _ptr(G), _ld(G),
              seg.batch, C.c_void_p(seg.batch_seg_ptr.data_ptr() + 4 * b), _ptr(seg.seg_col),
              _ptr(seg.seg_ptr), _ptr(seg.ent_pos), _ptr(seg.ent_val), float(l1), float(l2),
              _ptr(a_t), float(beta1), float(beta2), float(eps), _stream_handle(W.device))
@@ -202,7 +201,10 @@ def w1_step(W: torch.Tensor, m: torch.Tensor, v: torch.Tensor, G: torch.Tensor,
     increment_version(v)
 
 
-class MLP:
+class MLP(MiniBatchTrainer):
+    permutation_only = False  # the reference's order is one, but any in-range order trains
+    _plan_epoch = plan_segmented_epoch
+
     def __init__(self, n_epochs=10, batch_size=1000, init_parameters=None, complete_prob=False,
                  add_hidden=True, regul_coefs=(5e-5, 5e-5), save_results=False,
                  hidden_layer_size=None, drop_out=False, drop_out_coefs=(0.5, 0.5),
@@ -241,11 +243,7 @@ class MLP:
         if init is not None and len(init) != (4 if self.add_hidden else 2):
             raise ValueError("init_parameters must be [W1, b1, W2, b2] (or [W, b] without a "
                              "hidden layer), as lasagne.layers.get_all_param_values gives them")
-        dev = self.device
-
-        def param(x, shape):
-            return torch.nn.Parameter(_as_tensor(x, shape, dev), requires_grad=False)
-
+        param = self._param
         # Lasagne GlorotUniform draws W1 then W2 from numpy's global stream, b = Constant(0.)
         W1 = _glorot_uniform(in_size, K) if init is None else init[0]
         self.W1 = param(W1, (in_size, K))
@@ -278,17 +276,6 @@ class MLP:
         if self.add_hidden:  # output layer first, as the reference adds them
             return dense.l1l2_penalty([self.W2, self.W1], [p2, p1])
         return dense.l1l2_penalty([self.W1], [p1])
-
-    def _input(self, X) -> gs.DeviceCSR:
-        if isinstance(X, gs.DeviceCSR):
-            Xd = X
-        elif sps.issparse(X):
-            Xd = _upload_cached(self._inputs, X.tocsr() if X.format != "csr" else X, self.device)
-        else:
-            raise ValueError("Input for this layer must be sparse")
-        if hasattr(self, "in_size") and Xd.n_cols != self.in_size:
-            raise ValueError(f"X has {Xd.n_cols} columns, the model {self.in_size}")
-        return Xd
 
     def _first_layer(self, Xd: gs.DeviceCSR) -> torch.Tensor:
         """rectify(X.W1 + b1) (the hidden layer's deterministic output), or the logits
@@ -329,39 +316,25 @@ class MLP:
                              "the number of distinct training labels (mlp.py:132)")
         return Y.astype(np.int32)
 
-    def _prepare_epoch(self, order) -> None:
-        """Host half of an epoch: the order cut into whole batches, checked once, uploaded;
-        its labels gathered once; the runs of batches each segmentation call takes."""
-        perm, self._runs, nb = plan_epoch(order, self._indptr_host, self.batch_size)
-        self._perm_host = perm
-        self._perm = torch.from_numpy(perm.astype(np.int32)).to(self.device)
-        self._y_epoch = self._y_train.index_select(0, self._perm.to(torch.int64))
-        self._n_batches = nb
-
     @torch.no_grad()
     def _run_batches(self):
-        """Device half of an epoch: every batch's step, no host synchronisation. Returns the
+        """Device half of an epoch (the host half: MiniBatchTrainer._prepare_epoch, which
+        gathers the epoch's labels): every batch's step, no host synchronisation. Returns the
         last batch's (train loss with the penalty, accuracy) as device scalars."""
         B, K, dev = self.batch_size, self.width, self.device
         X, opt = self.Xd, self.optimizer
         (l1, l2), pen2 = self._penalty_coefs()
-        act = GCG_ACT_RELU if self.add_hidden else GCG_ACT_NONE
+        act = "relu" if self.add_hidden else None
         loss = acc = None
         for first, stop, nnz_sel in self._runs:
             seg = BatchSegments(X, self._perm[first * B:stop * B], B, nnz_sel)
             for b in range(first, stop):
                 rows = self._perm[b * B:(b + 1) * B]
-                y = self._y_epoch[b * B:(b + 1) * B]
+                y = self._epoch_data[b * B:(b + 1) * B]
                 last = b == self._n_batches - 1
-                h = gs.empty_dense(B, K, dev)
                 gate = gs.empty_gate(B, K, dev) if self.add_hidden else None
-                with torch.cuda.device(dev):
-                    # plan-less, one wave per batch row; the order was range-checked on the host
-                    call("gcg_spmm_csr_f32_gate", X.n_rows, X.n_cols, X.nnz, _ptr(X.indptr),
-                         _ptr(X.indices), _ptr(X.data), _ptr(self.W1), K, K, _ptr(h),
-                         h.stride(0) if B > 1 else max(K, 1), _ptr(self.b1), act, _ptr(rows), B,
-                         _ptr(gate), gate.stride(0) if gate is not None and B > 1 else
-                         (K + 3) // 4 * 4, _stream_handle(dev))
+                # the order was range-checked on the host (plan_epoch)
+                h = gs.spmm_rows(X, self.W1, self.b1, rows, act=act, gate=gate)
                 opt.zero_grad()
                 h.requires_grad_(True)
                 with torch.enable_grad():
@@ -384,21 +357,11 @@ class MLP:
                 opt.apply()
         return loss, acc
 
-    def _train_epoch(self, order=None):
-        if order is None:
-            order = np.arange(self.Xd.n_rows)
-            np.random.shuffle(order)  # mlp.py:84-85, numpy's global stream
-        self._prepare_epoch(order)
-        return self._run_batches()
-
     @torch.no_grad()
     def fit(self, X_train, Y_train, X_dev, Y_dev, epoch_orders=None):
         """mlp.py:125-289. epoch_orders (tests, measurement): one order of the training rows per
         epoch instead of the np.random.shuffle draws."""
-        for X in (X_train, X_dev):
-            if not (isinstance(X, gs.DeviceCSR) or sps.issparse(X)):
-                raise ValueError("Input for this layer must be sparse")
-        in_size = X_train.shape[1]
+        in_size = self._check_inputs(X_train, X_dev)
         self.out_size = output_size(Y_train)
         log.info("output size is %d", self.out_size)
         if not self.hidden_layer_size:
@@ -408,45 +371,19 @@ class MLP:
         y_train, y_dev = self._labels(Y_train, "Y_train"), self._labels(Y_dev, "Y_dev")
         if X_train.shape[0] != y_train.size or X_dev.shape[0] != y_dev.size:
             raise ValueError("X and Y must have the same number of rows")
-        n_batches(X_train.shape[0], self.batch_size)  # n < B raises
-        if X_dev.shape[1] != in_size:
-            raise ValueError("X_train and X_dev differ in width")
-        self.Xd = X_train if isinstance(X_train, gs.DeviceCSR) else \
-            gs.DeviceCSR.from_scipy(X_train, self.device)
-        self.Xdev = X_dev if isinstance(X_dev, gs.DeviceCSR) else \
-            gs.DeviceCSR.from_scipy(X_dev, self.device)
-        # the host copy of indptr: the sizes of every segmentation call (copied once)
-        self._indptr_host = (np.asarray(X_train.indptr) if sps.issparse(X_train) and
-                             X_train.format == "csr" else self.Xd.indptr.cpu().numpy()
-                             ).astype(np.int64)
+        self._upload_inputs(X_train, X_dev)
         self._build(in_size, self.out_size)
-        self._y_train = torch.from_numpy(y_train).to(self.device)
+        self._train_data = torch.from_numpy(y_train).to(self.device)
         y_dev_d = torch.from_numpy(y_dev).to(self.device)
         log.info("training (n_epochs, batch_size) = (%d, %d)", self.n_epochs, self.batch_size)
         self.history = []
-        best_params, best_val_loss, best_val_acc, n_down = None, float("inf"), 0.0, 0
-        for n in range(self.n_epochs):
-            order = None if epoch_orders is None else epoch_orders[n]
-            l_train, acc_train = self._train_epoch(order)
-            l_val, acc_val = self._evaluate(self.Xdev, y_dev_d)
-            l_train, acc_train, l_val, acc_val = (float(x) for x in
-                                                  (l_train, acc_train, l_val, acc_val))
-            if acc_val > best_val_acc:
-                best_val_loss, best_val_acc, n_down = l_val, acc_val, 0
-                best_params = [p.detach().clone() for p in self.params]
-            else:
-                n_down += 1
-            self.history.append({"epoch": n, "train_loss": l_train, "train_acc": acc_train,
-                                 "val_loss": l_val, "val_acc": acc_val})
-            log.info("epoch %d ,train_loss %s ,acc %s ,val_loss %s ,acc %s,best_val_acc %s", n,
-                     l_train, acc_train, l_val, acc_val, best_val_acc)
-            if n_down > self.early_stopping_max_down:
-                log.info("validation results went down. early stopping ...")
-                break
-        if best_params is not None:
-            for p, b in zip(self.params, best_params):
-                p.copy_(b)
-        self.best_val_loss = best_val_loss
+        # mlp.py:272-285: a strictly higher dev accuracy keeps the parameters
+        best, best_params = run_epochs(
+            lambda n: self._train_epoch(None if epoch_orders is None else epoch_orders[n]),
+            lambda: self._evaluate(self.Xdev, y_dev_d), self.params, self.history,
+            self.n_epochs, higher_accuracy, self.early_stopping_max_down)
+        self.best_val_loss = best[0]
+        restore(self.params, best_params)
         l_val, acc_val = self._evaluate(self.Xdev, y_dev_d)
         self.best_dev_loss, self.best_dev_acc = float(l_val), float(acc_val)
         log.info("Best dev acc: %f", self.best_dev_acc)

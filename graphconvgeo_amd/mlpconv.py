@@ -32,71 +32,24 @@ from typing import Optional
 
 import numpy as np
 import torch
-from torch.autograd.graph import increment_version
 
 from . import dense
 from . import sparse as gs
-from ._native import call
-from .sparse import _ptr, _stream_handle
 from .dropout import DropoutStream, SparseInputDropoutLayer, draw_seed
 from .layers import GATHER_DTYPES, ConvolutionDenseLayer, SparseConvolutionDenseLayer
+from .training import LasagneOptimizer, lower_loss, restore, run_epochs
 
 log = logging.getLogger(__name__)
 
 
-class LasagneAdam:
+class LasagneAdam(LasagneOptimizer):
     """lasagne.updates.adam: t += 1; a_t = lr*sqrt(1-b2^t)/(1-b1^t);
     m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g^2; p -= a_t*m/(sqrt(v)+eps)."""
 
-    def __init__(self, params, lr=4e-3, beta1=0.9, beta2=0.999, epsilon=1e-8):
-        self.params = list(params)
-        self.lr, self.beta1, self.beta2, self.eps = lr, beta1, beta2, epsilon
-        self.t = 0
-        self.m = [torch.zeros_like(p) for p in self.params]
-        self.v = [torch.zeros_like(p) for p in self.params]
-        # a_t lives on the device so a captured HIP graph reads the current step's value
-        self.a_t = torch.zeros((), dtype=torch.float32, device=self.params[0].device)
+    entry, second, lr = "gcg_adam_step_f32", "v", 4e-3
 
-    def prepare(self):
-        """Host half of a step: t += 1 and the bias-corrected step size (Python double,
-        rounded once to float32 exactly as an eager `a_t * m` would round it)."""
-        self.t += 1
-        a_t = self.lr * math.sqrt(1 - self.beta2 ** self.t) / (1 - self.beta1 ** self.t)
-        self.a_t.fill_(a_t)
-
-    @torch.no_grad()
-    def apply(self):
-        """Device half of a step (capturable): one fused HIP launch per parameter
-        (gcg_adam_step_f32) instead of ~8 elementwise torch kernels."""
-        for p, m, v in zip(self.params, self.m, self.v):
-            g = p.grad.contiguous()
-            if not p.is_contiguous():
-                raise ValueError("LasagneAdam needs contiguous parameters")
-            with torch.cuda.device(p.device):
-                call("gcg_adam_step_f32", p.numel(), _ptr(p), _ptr(g), _ptr(m), _ptr(v),
-                     _ptr(self.a_t), self.beta1, self.beta2, self.eps, _stream_handle(p.device))
-            # an in-place write through a raw pointer: bump the version counters as a torch
-            # in-place op would, so the padded weight copies (dense._WeightCache) follow
-            increment_version(p)
-            increment_version(m)
-            increment_version(v)
-
-    def step(self):
-        self.prepare()
-        self.apply()
-
-    def state(self):
-        return {"t": self.t, "m": [x.clone() for x in self.m], "v": [x.clone() for x in self.v]}
-
-    @torch.no_grad()
-    def load_state(self, st):
-        self.t = st["t"]
-        for dst, src in zip(self.m + self.v, st["m"] + st["v"]):
-            dst.copy_(src)
-
-    def zero_grad(self):
-        for p in self.params:
-            p.grad = None
+    def step_size(self, t):
+        return self.lr * math.sqrt(1 - self.beta2 ** t) / (1 - self.beta1 ** t)
 
 
 def trainer_order(order: str, in_size: int, n_classes: int) -> str:
@@ -141,35 +94,15 @@ def check_labels(Y) -> np.ndarray:
 def fit_loop(train_step, evaluate, params, history, n_epochs, report_k_epoch,
              early_stopping_max_down):
     """The reference's epoch loop (mlpconv.py:290-318) for both full-batch trainers, so that
-    every rank of the partitioned one takes the decisions the single-GPU one takes.
-    train_step() -> (loss, acc) runs one epoch; evaluate() -> (loss, acc) is the dev set's,
-    called every report_k_epoch epochs. A strictly lower dev loss snapshots `params`; more than
-    early_stopping_max_down validations without one stop the loop. One record per epoch is
-    appended to `history`. At the end the best snapshot (if any) is copied back into `params`
+    every rank of the partitioned one takes the decisions the single-GPU one takes: training's
+    run_epochs with the strictly-lower-dev-loss rule. train_step() -> (loss, acc) runs one epoch
+    and is read back at once; evaluate() -> (loss, acc) is the dev set's, called every
+    report_k_epoch epochs. At the end the best snapshot (if any) is copied back into `params`
     and the dev set is evaluated once more (mlpconv.py:316-318): that (loss, acc) is returned."""
-    best_params, best_val_loss, best_val_acc, n_down = None, math.inf, 0.0, 0
-    for n in range(n_epochs):
-        loss, acc = train_step()
-        rec = {"epoch": n, "train_loss": float(loss), "train_acc": float(acc)}
-        history.append(rec)
-        if n % report_k_epoch != 0:
-            continue
-        l_val, a_val = (float(x) for x in evaluate())
-        rec.update(val_loss=l_val, val_acc=a_val)
-        if l_val < best_val_loss:
-            best_val_loss, best_val_acc, n_down = l_val, a_val, 0
-            best_params = [p.detach().clone() for p in params]
-        else:
-            n_down += 1
-        log.info("epoch %d ,train_loss %s ,acc %s ,val_loss %s ,acc %s,best_val_acc %s",
-                 n, rec["train_loss"], rec["train_acc"], l_val, a_val, best_val_acc)
-        if n_down > early_stopping_max_down:
-            log.info("validation results went down. early stopping ...")
-            break
-    if best_params is not None:
-        with torch.no_grad():
-            for p, b in zip(params, best_params):
-                p.copy_(b)
+    _best, best_params = run_epochs(lambda n: [float(x) for x in train_step()], evaluate, params,
+                                    history, n_epochs, lower_loss, early_stopping_max_down,
+                                    validate_every=report_k_epoch)
+    restore(params, best_params)
     l_val, a_val = evaluate()
     return float(l_val), float(a_val)
 

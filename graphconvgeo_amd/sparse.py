@@ -620,6 +620,12 @@ def row_stride(k: int) -> int:
     return (k + 31) // 32 * 32  # 128-B aligned rows: every row on the minimal line count
 
 
+def _ld(t: torch.Tensor) -> int:
+    """The leading dimension the C entries take for a 2-D tensor with unit column stride: its
+    row stride, or its width (at least 1) where a single row's stride says nothing."""
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
+
+
 def empty_dense(n: int, k: int, device, pad_to: int = 4) -> torch.Tensor:
     """[n, k] float32 view of an [n, ld] buffer, ld = row_stride(k) (pad_to = 4) or k rounded
     up to pad_to: rows 16-B aligned, so the kernels can use dwordx4 loads/stores whatever K
@@ -720,6 +726,44 @@ def _gathers_bf16x8(Z, ldz: int, Y, ldy: int, bias) -> bool:
     return bias is None or bias.data_ptr() % 16 == 0
 
 
+def spmm_rows(X: DeviceCSR, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
+              rows: Optional[torch.Tensor] = None, vals: Optional[torch.Tensor] = None,
+              act: Optional[str] = None, gate: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(X[rows] . W + bias), plan-less, one wave per output row (gcg_spmm_csr_f32_gate; every
+    entry summed in storage order): the forward of a mini-batch, and spmm's float32 'rowwise'.
+
+    The contract is the caller's: rows is a contiguous int32 device tensor of row ids it has
+    range-checked against X.n_rows (None: every row, in order) -- nothing here reads rows back
+    to the host, so a batch costs no synchronisation, and the kernel indexes indptr with what
+    it is given. Ids may repeat and need no order. vals: a contiguous float32[X.nnz] device
+    array read in place of X.data (the values behind an input-dropout mask). W: float32
+    [X.n_cols, K], unit column stride. act / gate / out as spmm's: gate (empty_gate, 'relu'
+    only) receives the rectify gate bytes, out defaults to empty_dense(n_out, K)."""
+    dev = X.device
+    if W.dtype != torch.float32 or W.dim() != 2 or W.shape[0] != X.n_cols or W.device != dev or \
+            (W.shape[1] > 1 and W.stride(1) != 1):
+        raise ValueError(f"W must be float32 [{X.n_cols}, K] with unit column stride on {dev}")
+    if rows is not None and (rows.dtype != torch.int32 or rows.dim() != 1 or rows.device != dev
+                             or not rows.is_contiguous()):
+        raise TypeError(f"rows must be a contiguous 1-D int32 tensor on {dev}")
+    if vals is not None and (vals.dtype != torch.float32 or vals.numel() != X.nnz or
+                             vals.device != dev or not vals.is_contiguous()):
+        raise ValueError(f"vals must be a contiguous float32[{X.nnz}] tensor on {dev}")
+    K = W.shape[1]
+    n_out = X.n_rows if rows is None else rows.numel()
+    if out is None:
+        out = empty_dense(n_out, K, dev)
+    if n_out == 0 or K == 0:
+        return out
+    ldg = 0 if gate is None else gate.stride(0) if n_out > 1 else (K + 3) // 4 * 4
+    with torch.cuda.device(dev):
+        call("gcg_spmm_csr_f32_gate", X.n_rows, X.n_cols, X.nnz, _ptr(X.indptr), _ptr(X.indices),
+             _ptr(X.data if vals is None else vals), _ptr(W), _ld(W), K, _ptr(out), _ld(out),
+             _ptr(bias), ACTS[act], _ptr(rows), n_out, _ptr(gate), ldg, _stream_handle(dev))
+    return out
+
+
 def spmm(A: DeviceCSR, Z: torch.Tensor, bias: Optional[torch.Tensor] = None,
          act: Optional[str] = None, rows=None, mode: str = "auto",
          out: Optional[torch.Tensor] = None, task_nnz: int = 0,
@@ -793,12 +837,13 @@ def spmm(A: DeviceCSR, Z: torch.Tensor, bias: Optional[torch.Tensor] = None,
             raise ValueError("gate needs a 4-B aligned base and row stride % 4 == 0 (empty_gate)")
     if n_out == 0 or K == 0:
         return out
-    ldz = Z.stride(0) if Z.shape[0] > 1 else max(K, 1)
-    ldy = out.stride(0) if n_out > 1 else max(K, 1)
-    stream = _stream_handle(A.device)
-    actc = ACTS[act]
     if mode == "auto":
         mode = resolve_auto(A)
+    if mode == "rowwise" and not bf16:
+        return spmm_rows(A, Z, bias, rows_dev, act=act, gate=gate, out=out)
+    ldz, ldy = _ld(Z), _ld(out)
+    stream = _stream_handle(A.device)
+    actc = ACTS[act]
     with torch.cuda.device(A.device):
         if bf16 and mode == "rowwise":
             call("gcg_spmm_csr_bf16z_f32", A.n_rows, A.n_cols, A.nnz, _ptr(A.indptr),
@@ -814,10 +859,6 @@ def spmm(A: DeviceCSR, Z: torch.Tensor, bias: Optional[torch.Tensor] = None,
             call("gcg_spmm_csr_bf16z_f32_planned", plan.handle, _ptr(A.indptr), _ptr(A.indices),
                  _ptr(A.data), _ptr(Z), ldz, K, _ptr(out), ldy, _ptr(bias), actc, _ptr(gate), ldg,
                  _ptr(ws), 0 if ws is None else ws.numel() * 4, _ptr(hint), stream)
-        elif mode == "rowwise":
-            call("gcg_spmm_csr_f32_gate", A.n_rows, A.n_cols, A.nnz, _ptr(A.indptr),
-                 _ptr(A.indices), _ptr(A.data), _ptr(Z), ldz, K, _ptr(out), ldy, _ptr(bias), actc,
-                 _ptr(rows_dev), n_out, _ptr(gate), ldg, stream)
         else:
             plan = A.plan(sel, ordered=ORDERED_PLAN if mode == "ordered" else 0,
                           task_nnz=task_nnz)

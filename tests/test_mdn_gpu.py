@@ -15,7 +15,7 @@ from graphconvgeo_amd import dropout as D
 from graphconvgeo_amd import mdn as M
 from graphconvgeo_amd import mlp
 from graphconvgeo_amd import sparse as gs
-from graphconvgeo_amd._native import GCG_ACT_NONE, call
+from graphconvgeo_amd._native import call
 from graphconvgeo_amd.sparse import _ptr, _stream_handle
 from graphconvgeo_amd.synth import glorot_uniform, synthetic_features
 from test_mlp_gpu import ragged_csr
@@ -239,9 +239,7 @@ def check_dropout_segments(cuda, X, perm, B, p, seed=(5 << 32) | 987654321, step
         W = np.random.default_rng(b).standard_normal((X.shape[1], K)).astype(np.float32)
         Wd = torch.from_numpy(W).to(cuda)
         out = torch.empty((B, K), dtype=torch.float32, device=cuda)
-        call("gcg_spmm_csr_f32_gate", Xd.n_rows, Xd.n_cols, Xd.nnz, _ptr(Xd.indptr),
-             _ptr(Xd.indices), _ptr(vals_drop), _ptr(Wd), K, K, _ptr(out), K, None, GCG_ACT_NONE,
-             _ptr(perm_d[b * B:(b + 1) * B]), B, None, 0, _stream_handle(cuda))
+        gs.spmm_rows(Xd, Wd, rows=perm_d[b * B:(b + 1) * B], vals=vals_drop, out=out)
         assert np.array_equal(out.cpu().numpy().view(np.int32), (Xb @ W).view(np.int32)), b
     assert np.all(vd[~touched] == -5.0)  # rows outside the order are not written
     return seg, plain, stream, spec, vals_drop

@@ -549,3 +549,44 @@ def test_ordered_sliced_hub_rows_bitwise(cuda, K, task_nnz):
             g.replay()
             torch.cuda.synchronize()
             assert np.array_equal(out.cpu().numpy(), ref)
+
+
+@pytest.mark.parametrize("K", [1, 5])
+@pytest.mark.parametrize("rows", [[4], [5, 2, 4, 5]])
+def test_spmm_rows_reads_the_given_values_and_rows(cuda, K, rows):
+    """sparse.spmm_rows (the mini-batch forward): X[rows] . W + b with X's values taken from a
+    second array, row ids unsorted and repeated, one output row and several (the leading
+    dimensions of a single row), an empty row and a one-entry row. Small integers, so every
+    float32 sum is exact: equal to sparse.spmm on a matrix that holds the second array, and to
+    the dense product; with rectify and a gate, the same."""
+    indptr = np.array([0, 3, 5, 5, 9, 10, 13], np.int32)  # row 2 empty, row 4 one entry
+    indices = np.array([0, 3, 6, 1, 2, 0, 2, 4, 5, 3, 1, 5, 6], np.int32)
+    data = np.arange(1, 14, dtype=np.float32)
+    other = np.array([-3, 2, 5, -1, 4, 7, -6, 1, 3, -2, 6, -4, 2], np.float32)
+    X = gs.DeviceCSR.from_scipy(sps.csr_matrix((data, indices, indptr), shape=(6, 7)), cuda)
+    S = sps.csr_matrix((other, indices, indptr), shape=(6, 7))
+    Xo = gs.DeviceCSR.from_scipy(S, cuda)
+    assert torch.equal(X.indices, Xo.indices) and not torch.equal(X.data, Xo.data)
+    rng = np.random.default_rng(K)
+    W = rng.integers(-4, 5, (7, K)).astype(np.float32)
+    b = rng.integers(-3, 4, K).astype(np.float32)
+    Wd, bd, vals = to_dev(W, cuda), to_dev(b, cuda), to_dev(other, cuda)
+    rows_d = torch.tensor(rows, dtype=torch.int32, device=cuda)
+    pre = S.toarray()[rows] @ W + b
+    Y = gs.spmm_rows(X, Wd, bd, rows_d, vals=vals)
+    assert Y.shape == (len(rows), K)
+    assert torch.equal(Y, gs.spmm(Xo, Wd, bias=bd, rows=rows_d))
+    assert np.array_equal(Y.cpu().numpy(), pre)
+    assert np.array_equal(gs.spmm_rows(X, Wd, bd, rows_d).cpu().numpy(),
+                          sps.csr_matrix((data, indices, indptr), shape=(6, 7)).toarray()[rows]
+                          @ W + b)  # vals defaults to X.data
+    gate, gate_o = gs.empty_gate(len(rows), K, cuda), gs.empty_gate(len(rows), K, cuda)
+    Yr = gs.spmm_rows(X, Wd, bd, rows_d, vals=vals, act="relu", gate=gate)
+    assert torch.equal(Yr, gs.spmm(Xo, Wd, bias=bd, act="relu", rows=rows_d, gate=gate_o))
+    assert torch.equal(gate, gate_o)
+    assert np.array_equal(Yr.cpu().numpy(), np.maximum(pre, 0))
+    assert np.array_equal(gate.cpu().numpy(), (2 * (pre > 0) + (pre == 0)).astype(np.uint8))
+    with pytest.raises(TypeError):
+        gs.spmm_rows(X, Wd, bd, rows_d.to(torch.int64))
+    with pytest.raises(ValueError):
+        gs.spmm_rows(X, Wd, bd, rows_d, vals=vals[:-1])
