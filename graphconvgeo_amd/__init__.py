@@ -21,6 +21,8 @@ Product modules (all compute runs in libgcg_spmm.so HIP kernels; no CPU fallback
                cross-entropy against sparse soft targets, Adamax, NNModel_loc2lang (lat/lon -> words)
   kmeans       get_cluster_centers: k-means++ / Lloyd k-means and the per-cluster statistics that
                start the mixture models' Gaussians, float64 on the GPU
+  dialect      the dialect-embedding evaluation (main.py:108-162, 230-281, 364-384): min-max + l1
+               scaling, the rank of every gold word among all V neighbours, recall@k, kneighbors
   synth        seeded synthetic graphs / features for the BASELINE configs
 
 `MLP`, `input_convolution`, `NNModel_lang2loc`, `NNModel_lang2locshared`, `NNModel_loc2lang` and
@@ -39,7 +41,8 @@ __version__ = "0.1.0"
 _os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "8")
 
 __all__ = ["sparse", "ops", "layers", "dense", "distributed", "dist_train", "graph", "mentions",
-           "training", "mlpconv", "mlp", "geo", "mdn", "loc2lang", "synth", "MLP",
+           "training", "mlpconv", "mlp", "geo", "mdn", "loc2lang", "dialect", "synth",
+           "MLP",
            "input_convolution",
            "NNModel_lang2loc", "NNModel_lang2locshared", "NNModel_loc2lang", "DeviceCSR"]
 

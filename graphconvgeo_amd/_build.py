@@ -17,11 +17,13 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 # SpGEMM, MFMA dense projection + softmax/xent, Philox dropout, the mini-batch MLP's epoch
 # segmentation and W1 step, k-d-tree labels + geolocation metrics, the mixture-density location
 # head with the Gaussian layer of the inverse model, the softmax cross-entropy against sparse
-# soft targets, the k-means initialisation of the Gaussian components, error/version helpers.
+# soft targets, the k-means initialisation of the Gaussian components, the dialect-embedding
+# evaluation (scaling, neighbour ranks, kneighbors), error/version helpers.
 # Compiled in parallel, linked into one shared library.
 SOURCES = [os.path.join(CSRC, f) for f in
            ("spmm.hip", "spmm_bf16.hip", "csr_ops.hip", "graph_build.hip", "spgemm.hip", "dense.hip", "dropout.hip",
-            "minibatch.hip", "geo.hip", "kmeans.hip", "mdn.hip", "softmax_csr.hip", "errors.cpp")]
+            "minibatch.hip", "geo.hip", "kmeans.hip", "mdn.hip", "softmax_csr.hip", "neighbours.hip",
+            "errors.cpp")]
 INTERNAL_HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "spmm_shared.h", "index_kernels.h",
                                                     "gemm_epilogue.inc", "philox.h",
                                                     "rectify_backward_pass.inc",

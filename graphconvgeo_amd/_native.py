@@ -172,6 +172,16 @@ SIGNATURES = {
     "gcg_cluster_stats_f64_workspace_bytes": (C.c_int, [_i64, _i64, _psz]),
     "gcg_cluster_stats_f64": (C.c_int, [_i64, _p, _p, _i64, C.c_int, _p, _p, _p, _p, _p, _p,
                                         C.c_size_t, _p]),
+    # the dialect-embedding evaluation (csrc/neighbours.hip)
+    "gcg_neighbours_tile": (C.c_int32, [C.c_int32]),
+    "gcg_minmax_l1_rows_f32_workspace_bytes": (C.c_int, [_i64, _i64, _psz]),
+    "gcg_minmax_l1_rows_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _i64, _p, _p, C.c_size_t, _p]),
+    "gcg_neighbour_ranks_f32_workspace_bytes": (C.c_int, [_i64, _i64, _psz]),
+    "gcg_neighbour_ranks_f32": (C.c_int, [_i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p,
+                                          _p, C.c_size_t, _p]),
+    "gcg_kneighbors_f32_workspace_bytes": (C.c_int, [_i64, _i64, _i64, _psz]),
+    "gcg_kneighbors_f32": (C.c_int, [_i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p,
+                                     C.c_size_t, _p]),
     "gcg_spgemm_ex": (C.c_int, [_i64, _i64, _i64, _i64, _p, _p, _p, C.c_int, _i64, _p, _p, _p,
                                 C.c_int, _i64, _p, _p, _p, _p, C.c_int32, _i64, _p]),
 }

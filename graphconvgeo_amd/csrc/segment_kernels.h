@@ -1,5 +1,5 @@
-// segment_kernels.h -- what geo.hip and kmeans.hip share: the grid-stride helpers and the
-// class pointer of a sorted label list (internal, not part of the C-ABI).
+// segment_kernels.h -- what geo.hip, kmeans.hip and neighbours.hip share: the grid-stride
+// helpers and the class pointer of a sorted label list (internal, not part of the C-ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,8 +17,9 @@ __device__ __forceinline__ int64_t grid_stride() {
 }
 
 // ptr[c] = the first position of class c in the sorted labels (ptr[C] = N).
-__global__ void class_ptr_kernel(int64_t N, int64_t C, const int32_t* __restrict__ sorted,
-                                 int32_t* __restrict__ ptr) {
+[[maybe_unused]] __global__ void class_ptr_kernel(int64_t N, int64_t C,
+                                                  const int32_t* __restrict__ sorted,
+                                                  int32_t* __restrict__ ptr) {
   for (int64_t p = grid_start(); p <= N; p += grid_stride()) {
     const int64_t prev = p == 0 ? -1 : sorted[p - 1];
     const int64_t cur = p == N ? C : sorted[p];

@@ -408,11 +408,13 @@ class MLP(MiniBatchTrainer):
         return self.accuracy(X_test, Y_test)
 
     @torch.no_grad()
-    def get_embedding(self, X):
-        """The hidden layer's deterministic output (mlp.py:201-202, 310-311)."""
+    def get_embedding(self, X, as_tensor: bool = False):
+        """The hidden layer's deterministic output (mlp.py:201-202, 310-311): a NumPy array, or
+        with as_tensor the float32 device tensor itself (what dialect.eval_embeddings takes)."""
         if not self.add_hidden:
             raise ValueError("get_embedding needs add_hidden=True (mlp.py:200-202)")
-        return self._first_layer(self._input(X)).cpu().numpy()
+        emb = self._first_layer(self._input(X))
+        return emb if as_tensor else emb.cpu().numpy()
 
     def get_params(self):
         return [p.detach().cpu().numpy() for p in self.params]

@@ -1114,6 +1114,88 @@ gcg_status gcg_cluster_stats_f64(int64_t N, const double* locs, const int32_t* l
                                  int32_t* status_dev, void* workspace, size_t workspace_bytes,
                                  gcg_stream_t stream);
 
+/*
+ * The dialect-embedding evaluation (csrc/neighbours.hip): main.py's eval_embeddings (364-384),
+ * nearest_neighbours (108-162) and what recall_at_k (230-281) needs of it, on resident float32
+ * embeddings E (V x D, row stride lde >= D, V <= 2^31 - 2) and queries (Q x D, row stride ldq).
+ *
+ * The distance and the order, everywhere below: d2(q, e) = one float32 accumulator, from +0,
+ * taking acc = fma(d, d, acc) with d = q_j - e_j (rounded once) for j = 0, 1, ..., D - 1 in
+ * that order. It is the difference form (no cancellation: relative error at most
+ * (D + 2) 2^-24 / (1 - (D + 2) 2^-24), exact on small integers) and the same (query, row) pair
+ * has the same bits in every entry. Words are ordered by (d2 as float32, row index) ascending.
+ *
+ * Conventions as above: caller-owned buffers and workspaces (*_workspace_bytes; 256-B aligned),
+ * no entry synchronizes the stream, *status_dev (device int32, reset by every call) reports
+ * data errors, and every result is bitwise the same from call to call: sums run in a fixed
+ * order and the only atomics add integers.
+ *
+ * gcg_neighbours_tile(which): the sizes a caller's tests want to sit on.
+ */
+enum {
+  GCG_NEIGHBOURS_ROW_TILE = 0,         /* rows of E per workgroup of the distance pass (256) */
+  GCG_NEIGHBOURS_QUERY_TILE = 1,       /* queries per workgroup, Q > the small tile (32) */
+  GCG_NEIGHBOURS_QUERY_TILE_SMALL = 2, /* ... for Q <= 8 (8) */
+  GCG_NEIGHBOURS_SLOT_CAP = 3,         /* pairs of a query tile counted in LDS; more go to HBM */
+  GCG_NEIGHBOURS_COL_CHUNK = 4,        /* columns staged through LDS per step (32) */
+  GCG_NEIGHBOURS_MAX_K = 5,            /* the largest k of gcg_kneighbors_f32 (1024) */
+  GCG_NEIGHBOURS_MINMAX_ROWS = 6,      /* rows per workgroup of the column min / max (1024) */
+  GCG_NEIGHBOURS_MERGE_SLICE = 7       /* kneighbors candidates per first-level merge (8192) */
+};
+int32_t gcg_neighbours_tile(int32_t which); /* 0 for an unknown `which` */
+
+/*
+ * eval_embeddings' preprocessing (main.py:373-377): sklearn's MinMaxScaler(0, 1) and
+ * normalize(norm='l1'). Two passes over E. The first takes every column's minimum and maximum
+ * (row blocks of 1024 in ascending order, no atomics). The second is fused, one wave per row:
+ * y_j = x_j * scale_j + (0 - min_j * scale_j), scale_j = 1 / (max_j - min_j) or 1 where
+ * max_j == min_j, in float64; the row's sum of |y_j| in a fixed order; out_j = y_j / sum rounded
+ * to float32. A row whose sum is 0 keeps y. `out` (V x D, row stride ldo) must not overlap E;
+ * columns past D of either are neither read nor written. *status_dev = 1 for a non-finite
+ * element of E (the output is then meaningless).
+ */
+gcg_status gcg_minmax_l1_rows_f32_workspace_bytes(int64_t V, int64_t D, size_t* bytes);
+gcg_status gcg_minmax_l1_rows_f32(int64_t V, int64_t D, const float* E, int64_t lde, float* out,
+                                  int64_t ldo, int32_t* status_dev, void* workspace,
+                                  size_t workspace_bytes, gcg_stream_t stream);
+
+/*
+ * rank[p] = #{v in [0, V) : (d2(q_p, v), v) < (d2(q_p, w_p), w_p)} for the P pairs
+ * (q_p, w_p = pair_word[p]) grouped by query: query q owns pairs [pair_ptr[q], pair_ptr[q + 1]).
+ * That is the 0-based position of word w_p in the full ordering of the V words for query q_p,
+ * which is all recall@k needs. The thresholds d2(q_p, w_p) are computed first and sorted inside
+ * each query; then E is read once per tile of 32 queries (8 when Q <= 8): a workgroup owns 256
+ * rows, computes each d2(q, v) once, finds by binary search the first threshold of q above it
+ * and adds 1 to that slot (in LDS when the tile has at most GCG_NEIGHBOURS_SLOT_CAP pairs); a
+ * prefix sum over each query's slots gives the ranks. No Q x V array is written. A query tile
+ * without pairs costs nothing.
+ *   status_dev  1 a non-finite element or distance, 2 a word outside [0, V), 3 pair_ptr is not
+ *               0 = ptr[0] <= ... <= ptr[Q] = P (no rank is then computed); ranks are
+ *               meaningless unless it is 0
+ */
+gcg_status gcg_neighbour_ranks_f32_workspace_bytes(int64_t Q, int64_t P, size_t* bytes);
+gcg_status gcg_neighbour_ranks_f32(int64_t V, int64_t D, const float* E, int64_t lde, int64_t Q,
+                                   const float* queries, int64_t ldq, int64_t P,
+                                   const int32_t* pair_ptr, const int32_t* pair_word,
+                                   int32_t* rank, int32_t* status_dev, void* workspace,
+                                   size_t workspace_bytes, gcg_stream_t stream);
+
+/*
+ * The k smallest (d2, row) of every query in order: dist2[Q x k] and index[Q x k], so that
+ * index[q * k + r] == w exactly when rank(q, w) == r. 1 <= k <= min(V, 1024), else
+ * GCG_ERR_INVALID_ARG (the full ordering is what gcg_neighbour_ranks_f32 is for). The distance
+ * pass is the rank entry's (the same query tiles); every tile of 256 rows then sorts its keys in
+ * LDS and keeps its first min(k, 256) per query, and one workgroup per query merges them (in
+ * two levels above 8192 candidates: up to 64 slices, then the slices' k each). The workspace
+ * holds the candidates, Q * ceil(V / 256) * min(k, 256) * 8 bytes, and the slices' results.
+ * *status_dev = 1 for a non-finite element.
+ */
+gcg_status gcg_kneighbors_f32_workspace_bytes(int64_t V, int64_t Q, int64_t k, size_t* bytes);
+gcg_status gcg_kneighbors_f32(int64_t V, int64_t D, const float* E, int64_t lde, int64_t Q,
+                              const float* queries, int64_t ldq, int64_t k, float* dist2,
+                              int32_t* index, int32_t* status_dev, void* workspace,
+                              size_t workspace_bytes, gcg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
