@@ -250,5 +250,27 @@ def call(name: str, *args) -> None:
         raise NativeError(name, st, msg)
 
 
+def workspace_bytes(fn: str, *sizes) -> int:
+    """What the `..._workspace_bytes` entry `fn` reports for these sizes."""
+    nbytes = C.c_size_t()
+    call(fn, *sizes, C.byref(nbytes))
+    return nbytes.value
+
+
+def workspace(fn: str, dev, *sizes):
+    """(ws, nbytes): a device buffer of workspace_bytes(fn, *sizes) bytes (at least one, so it
+    has an address; the allocator aligns it far past the 8 bytes any entry asks for) and the
+    byte count to pass with it."""
+    import torch
+
+    nbytes = workspace_bytes(fn, *sizes)
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), nbytes
+
+
+def device_scalar(x):
+    """A device scalar as the float32 [1] tensor a `scale_dev` argument points at; None stays."""
+    return None if x is None else x.reshape(1).float().contiguous()
+
+
 def version() -> str:
     return load().gcg_version().decode()

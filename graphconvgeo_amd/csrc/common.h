@@ -41,5 +41,20 @@ namespace {  // small device helpers, one copy per translation unit
 
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// Butterfly reductions over the wave (lane ^ 32, 16, ..., 1), float or double: the same order
+// for every lane, every launch, and the result in every lane.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
+  return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+  return v;
+}
+
 }  // namespace
 }  // namespace gcg

@@ -16,43 +16,139 @@ namespace {
 
 constexpr int kMaxComp = 1024;
 constexpr float kLatScale = 90.0f, kLonScale = 180.0f, kSigmaScale = 10.0f;
-constexpr float kLog2Pi = 1.8378770664093453f;   // log(2 pi)
-constexpr float kInv2Pi = 0.15915494309189535f;  // 0.5 / pi
+constexpr double kLog2Pi = 1.8378770664093453;                                   // log(2 pi)
+constexpr float kLog2PiF = 1.8378770664093453f, kInv2Pi = 0.15915494309189535f;  // and 0.5 / pi
 
-// ---- the transforms of one component (lang2loc.py:143-160) ----------------------------------
+// ---- the bivariate Gaussian, stated once ----------------------------------------------------
+// Each formula of the models below, in T = float or double as its caller computes it: built
+// with -ffp-contract=off, an inlined piece rounds as its expression reads (exp(float) is expf).
 
 // softplus in its stable form: max(x, 0) + log1p(exp(-|x|)).
-__device__ __forceinline__ float softplus(float x) {
-  return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x)));
+template <typename T>
+__device__ __forceinline__ T softplus(T x) {
+  return fmax(x, T(0)) + log1p(exp(-fabs(x)));
 }
 
 // The sigmoid, softplus's derivative, without overflow on either side.
-__device__ __forceinline__ float sigmoid(float x) {
-  const float t = expf(-fabsf(x));
-  return x >= 0.0f ? 1.0f / (1.0f + t) : t / (1.0f + t);
+template <typename T>
+__device__ __forceinline__ T sigmoid(T x) {
+  const T t = exp(-fabs(x));
+  return x >= T(0) ? T(1) / (T(1) + t) : t / (T(1) + t);
 }
 
 // rho = softsign(t) and 1 - rho^2 = (1 + 2|t|) / (1 + |t|)^2 from the raw value (no
 // cancellation as |rho| -> 1).
+template <typename T>
 struct Corr {
-  float rho, q, inv1;  // inv1 = 1 / (1 + |t|); d rho / d t = inv1^2
+  T rho, q, inv1;  // inv1 = 1 / (1 + |t|); d rho / d t = inv1^2
 };
-__device__ __forceinline__ Corr corr_of(float t) {
-  const float a = fabsf(t);
-  const float inv1 = 1.0f / (1.0f + a);
-  return Corr{t * inv1, (1.0f + 2.0f * a) * (inv1 * inv1), inv1};
+template <typename T>
+__device__ __forceinline__ Corr<T> corr_of(T t) {
+  const T a = fabs(t);
+  const T inv1 = T(1) / (T(1) + a);
+  return Corr<T>{t * inv1, (T(1) + T(2) * a) * (inv1 * inv1), inv1};
 }
 
-// Butterfly reductions over the wave: the same order for every lane, every launch.
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  return v;
+// What depends on a shared component alone, in double: s1, s2 = softplus(raw), rho, q = 1 -
+// rho^2 and k = -log(2 pi) - (log s1 + log s2) - 0.5 log q, the row-independent part of e.
+// Double because e is: two components that compete for a row have |e| of 30 .. 1e4 there, and
+// their responsibilities hang on the difference -- float32 transforms and a float32 e leave
+// ulp(|e|) in it.
+struct Component {
+  double s1, s2, rho, q, k;
+};
+__device__ __forceinline__ Component component_constants(float r1, float r2, float cor) {
+  const double s1 = softplus<double>(r1), s2 = softplus<double>(r2);
+  const Corr<double> cr = corr_of<double>(cor);
+  return Component{s1, s2, cr.rho, cr.q, (-kLog2Pi - (log(s1) + log(s2))) - 0.5 * log(cr.q)};
 }
-__device__ __forceinline__ float wave_sum(float v) {
+
+// z = u1^2 + u2^2 - 2 rho u1 u2 of the scaled differences u_i = d_i / s_i. The caller forms
+// the differences: where and in which precision is what the models differ in.
+template <typename T>
+struct Quad {
+  T u1, u2, z;
+};
+template <typename T>
+__device__ __forceinline__ T quad_z(T u1, T u2, T rho) {
+  return (u1 * u1 + u2 * u2) - T(2) * rho * (u1 * u2);
+}
+template <typename T>
+__device__ __forceinline__ Quad<T> quad(T d1, T d2, T s1, T s2, T rho) {
+  const T u1 = d1 / s1, u2 = d2 / s2;
+  return Quad<T>{u1, u2, quad_z(u1, u2, rho)};
+}
+
+// The exponent e = -0.5 z / q + k of a shared component (k: component_constants).
+__device__ __forceinline__ double exponent(double z, double q, double k) {
+  return (-0.5 * z) / q + k;
+}
+
+// d e / d (mu1, mu2, s1, s2, rho), in that order, with a_i = (u_i - rho u_j) / q:
+//   a_i / s_i, (u_i a_i - 1) / s_i, (u1 u2 + rho (1 - z / q)) / q
+template <typename T>
+struct GradTerms {
+  T d[5];
+};
+template <typename T>
+__device__ __forceinline__ GradTerms<T> grad_terms(Quad<T> t, T s1, T s2, T rho, T q) {
+  const T a1 = (t.u1 - rho * t.u2) / q, a2 = (t.u2 - rho * t.u1) / q;
+  return GradTerms<T>{{a1 / s1, a2 / s2, (t.u1 * a1 - T(1)) / s1, (t.u2 * a2 - T(1)) / s2,
+                       (t.u1 * t.u2 + rho * (T(1) - t.z / q)) / q}};
+}
+
+// d parameter / d raw of plane j (mus lat, lon; sigmas lat, lon; corxy) of shared component c:
+// 1, sigmoid(raw), 1 / (1 + |raw|)^2.
+template <typename T>
+__device__ __forceinline__ T chain_factor(int j, int c, const float* __restrict__ sig,
+                                          const float* __restrict__ cor) {
+  if (j == 2 || j == 3) return sigmoid<T>(sig[2 * c + (j - 2)]);
+  if (j == 4) {
+    const T inv1 = corr_of<T>(cor[c]).inv1;
+    return inv1 * inv1;
+  }
+  return T(1);
+}
+
+// dparams[j][c] = float32(lead * chain_factor_j(c) * (partial of workgroup 0 + 1 + ... in
+// order)), the sum and the factor in T: thread per (j, c).
+template <typename T>
+__device__ __forceinline__ void finish_partials(int C, int groups, const T* __restrict__ partials,
+                                                const float* __restrict__ sig,
+                                                const float* __restrict__ cor, T lead,
+                                                float* __restrict__ dparams) {
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= 5 * C) return;
+  T s = T(0);
+  for (int g = 0; g < groups; ++g) s = s + partials[static_cast<int64_t>(g) * 5 * C + t];
+  const int j = t / C, c = t - j * C;
+  dparams[t] = static_cast<float>((lead * chain_factor<T>(j, c, sig, cor)) * s);
+}
+
+// The better of two (score, index) candidates: the higher score, the lower index on a tie.
+__device__ __forceinline__ void take_better(float& s, int& i, float s2, int i2) {
+  if (s2 > s || (s2 == s && i2 < i)) {
+    s = s2;
+    i = i2;
+  }
+}
+
+// The best candidate of the wave, in every lane and in the wave's slot.
+__device__ __forceinline__ void wave_best(float& s, int& i, int lane, float& slot_s, int& slot_i) {
 #pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
-  return v;
+  for (int off = kWave / 2; off > 0; off >>= 1)
+    take_better(s, i, __shfl_xor(s, off), __shfl_xor(i, off));
+  if (lane == 0) {
+    slot_s = s;
+    slot_i = i;
+  }
+}
+
+// The winner among wave 0's candidate (s, i) and the other waves' slots (ss, si). Every score NaN
+// leaves no winner: component 0, in bounds.
+__device__ __forceinline__ int winner_of(float s, int i, const float* ss, const int* si, int C) {
+  for (int w = 1; w < kWavesPerBlock; ++w) take_better(s, i, ss[w], si[w]);
+  return (i >= 0 && i < C) ? i : 0;
 }
 
 // The two halves of a log-sum-exp, kept apart: logsumexp = max + log(sum), while a softmax
@@ -118,13 +214,15 @@ __global__ __launch_bounds__(kBlock) void mdn_nll_kernel(
     const int c = lane + i * kWave;
     e[i] = -INFINITY;
     if (c < C) {
+      // the sigmas are kSigmaScale * softplus here; the shared components' are not scaled
       const float s1 = kSigmaScale * softplus(o[2 * C + c]);
       const float s2 = kSigmaScale * softplus(o[3 * C + c]);
-      const Corr k = corr_of(o[4 * C + c]);
-      const float u1 = mean_of(o[c], kLatScale, y1).d / s1;
-      const float u2 = mean_of(o[C + c], kLonScale, y2).d / s2;
-      const float z = (u1 * u1 + u2 * u2) - 2.0f * k.rho * (u1 * u2);
-      e[i] = ((((-0.5f * z) / k.q - kLog2Pi) - (logf(s1) + logf(s2))) - 0.5f * logf(k.q)) +
+      const Corr<float> k = corr_of(o[4 * C + c]);
+      const Quad<float> t = quad(mean_of(o[c], kLatScale, y1).d,
+                                 mean_of(o[C + c], kLonScale, y2).d, s1, s2, k.rho);
+      // log(2 pi), the log-sigmas and 0.5 log q leave one after another here, not as the
+      // shared components' precomputed k: another rounding, kept
+      e[i] = ((((-0.5f * t.z) / k.q - kLog2PiF) - (logf(s1) + logf(s2))) - 0.5f * logf(k.q)) +
              ((lg[i] - lp.max) - log_sum_pi);
     }
   }
@@ -143,18 +241,14 @@ __global__ __launch_bounds__(kBlock) void mdn_nll_kernel(
       const Mean m1 = mean_of(o[c], kLatScale, y1), m2 = mean_of(o[C + c], kLonScale, y2);
       const float r1 = o[2 * C + c], r2 = o[3 * C + c];
       const float s1 = kSigmaScale * softplus(r1), s2 = kSigmaScale * softplus(r2);
-      const Corr k = corr_of(o[4 * C + c]);
-      const float u1 = m1.d / s1, u2 = m2.d / s2;
-      const float z = (u1 * u1 + u2 * u2) - 2.0f * k.rho * (u1 * u2);
-      const float a1 = (u1 - k.rho * u2) / k.q, a2 = (u2 - k.rho * u1) / k.q;
-      // d e / d mu_i = a_i / s_i, d e / d s_i = (u_i a_i - 1) / s_i,
-      // d e / d rho = (u1 u2 + rho (1 - z / q)) / q; d loss / d e = -w
-      const float m = -(w * up);
-      g[c] = m * (a1 / s1) * m1.dmu;
-      g[C + c] = m * (a2 / s2) * m2.dmu;
-      g[2 * C + c] = m * ((u1 * a1 - 1.0f) / s1) * (kSigmaScale * sigmoid(r1));
-      g[3 * C + c] = m * ((u2 * a2 - 1.0f) / s2) * (kSigmaScale * sigmoid(r2));
-      g[4 * C + c] = m * ((u1 * u2 + k.rho * (1.0f - z / k.q)) / k.q) * (k.inv1 * k.inv1);
+      const Corr<float> k = corr_of(o[4 * C + c]);
+      const GradTerms<float> de = grad_terms(quad(m1.d, m2.d, s1, s2, k.rho), s1, s2, k.rho, k.q);
+      const float m = -(w * up);  // d loss / d e = -w
+      g[c] = m * de.d[0] * m1.dmu;
+      g[C + c] = m * de.d[1] * m2.dmu;
+      g[2 * C + c] = m * de.d[2] * (kSigmaScale * sigmoid(r1));
+      g[3 * C + c] = m * de.d[3] * (kSigmaScale * sigmoid(r2));
+      g[4 * C + c] = m * de.d[4] * (k.inv1 * k.inv1);
       g[5 * C + c] = (pi - w) * up;
     }
   }
@@ -211,14 +305,6 @@ __global__ __launch_bounds__(kBlock) void mdn_unpack_kernel(
 
 // ---- prediction -----------------------------------------------------------------------------
 
-// The better of two (score, index) candidates: the higher score, the lower index on a tie.
-__device__ __forceinline__ void take_better(float& s, int& i, float s2, int i2) {
-  if (s2 > s || (s2 == s && i2 < i)) {
-    s = s2;
-    i = i2;
-  }
-}
-
 // One workgroup per row. Six planes of the row are staged in LDS once:
 //   mu1, mu2, a1 = sqrt(h) / s1, a2 = sqrt(h) / s2 with h = 0.5 / (1 - rho^2), rho,
 //   w = pi * (0.5 / pi) / (s1 s2) * sqrt(1 / (1 - rho^2))
@@ -226,18 +312,18 @@ __device__ __forceinline__ void take_better(float& s, int& i, float s2, int i2) 
 // v_i = (x_i - mu_i) a_i -- the reference's expression with the factor -0.5 / (1 - rho^2) moved
 // inside the square. Thread t scores the candidates t, t + 256, ...: the sum over k ascending,
 // every lane reading the same k (an LDS broadcast). method 1 scores a candidate by its logit.
+// The factors and the term are written out here and in mdn_shared_density_kernel, not shared:
+// through inlined helpers the vectoriser packs the score loop another way and a row takes 0.5 %
+// (helpers for the factors alone) to 6 % (for the term too) longer at C = 900
+// (profiles/mdn/refactor_ab.md).
 __global__ __launch_bounds__(kBlock) void mdn_predict_kernel(
     int64_t B, int C, const float* __restrict__ O, int64_t ldo, int method,
     int32_t* __restrict__ idx, float* __restrict__ latlon) {
   extern __shared__ float lds[];
   __shared__ float best_s[kWavesPerBlock];
   __shared__ int best_i[kWavesPerBlock];
-  float* mu1 = lds;
-  float* mu2 = lds + C;
-  float* a1 = lds + 2 * C;
-  float* a2 = lds + 3 * C;
-  float* rho = lds + 4 * C;
-  float* wgt = lds + 5 * C;
+  float *mu1 = lds, *mu2 = lds + C, *a1 = lds + 2 * C, *a2 = lds + 3 * C;
+  float *rho = lds + 4 * C, *wgt = lds + 5 * C;
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
   for (int64_t r = blockIdx.x; r < B; r += gridDim.x) {
     const float* o = O + r * ldo;
@@ -258,7 +344,7 @@ __global__ __launch_bounds__(kBlock) void mdn_predict_kernel(
     for (int c = tid; c < C; c += kBlock) {
       const float s1 = kSigmaScale * softplus(o[2 * C + c]);
       const float s2 = kSigmaScale * softplus(o[3 * C + c]);
-      const Corr k = corr_of(o[4 * C + c]);
+      const Corr<float> k = corr_of(o[4 * C + c]);
       const float qi = 1.0f / k.q;
       const float sh = sqrtf(0.5f * qi);
       mu1[c] = kLatScale * tanhf(o[c]);
@@ -266,7 +352,9 @@ __global__ __launch_bounds__(kBlock) void mdn_predict_kernel(
       a1[c] = sh / s1;
       a2[c] = sh / s2;
       rho[c] = k.rho;
-      wgt[c] = method == 0 ? expf(o[5 * C + c] - m) / sum_pi * kInv2Pi * ((1.0f / s1) * (1.0f / s2)) * sqrtf(qi)
+      // the weight opens (pi * 1 / 2 pi) here, the density table's 1 / 2 pi: another rounding, kept
+      wgt[c] = method == 0 ? expf(o[5 * C + c] - m) / sum_pi * kInv2Pi *
+                                 ((1.0f / s1) * (1.0f / s2)) * sqrtf(qi)
                            : o[5 * C + c];
     }
     __syncthreads();
@@ -287,18 +375,10 @@ __global__ __launch_bounds__(kBlock) void mdn_predict_kernel(
       }
       take_better(bs, bi, score, c);  // ascending c: a later equal score never replaces
     }
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1)
-      take_better(bs, bi, __shfl_xor(bs, off), __shfl_xor(bi, off));
-    if (lane == 0) {
-      best_s[wave] = bs;
-      best_i[wave] = bi;
-    }
+    wave_best(bs, bi, lane, best_s[wave], best_i[wave]);
     __syncthreads();
     if (tid == 0) {
-      for (int w = 1; w < kWavesPerBlock; ++w) take_better(bs, bi, best_s[w], best_i[w]);
-      // every score NaN leaves no winner: component 0, in bounds
-      const int win = (bi >= 0 && bi < C) ? bi : 0;
+      const int win = winner_of(bs, bi, best_s, best_i, C);
       if (idx != nullptr) idx[r] = win;
       latlon[2 * r] = mu1[win];
       latlon[2 * r + 1] = mu2[win];
@@ -307,13 +387,15 @@ __global__ __launch_bounds__(kBlock) void mdn_predict_kernel(
   }
 }
 
-gcg_status check_layout(const char* fn, int64_t B, int64_t C, int64_t ldo) {
+// B rows of `planes` (6: a raw output, 1: logits or densities) times C columns at stride ld.
+gcg_status check_sizes(const char* fn, int64_t B, int64_t C, int64_t ld, int planes) {
   if (B < 0 || B > INT32_MAX || C < 1 || C > kMaxComp)
     return fail(GCG_ERR_INVALID_ARG, "%s: bad sizes B=%lld C=%lld (1 <= C <= %d)", fn,
                 static_cast<long long>(B), static_cast<long long>(C), kMaxComp);
-  if (ldo < 6 * C)
-    return fail(GCG_ERR_INVALID_ARG, "%s: row stride %lld < 6 C = %lld", fn,
-                static_cast<long long>(ldo), static_cast<long long>(6 * C));
+  if (ld < planes * C)
+    return fail(GCG_ERR_INVALID_ARG, "%s: row stride %lld < %s = %lld", fn,
+                static_cast<long long>(ld), planes == 1 ? "C" : "6 C",
+                static_cast<long long>(planes * C));
   return GCG_OK;
 }
 
@@ -349,31 +431,24 @@ int64_t shared_groups(int64_t B) {
   return (B + R - 1) / R;
 }
 
-// What depends on the component alone, once per call, in double: P [5, C] = s1, s2, rho, q and
-//   k = -log(2 pi) - (log s1 + log s2) - 0.5 log q, the row-independent part of e.
-// Double because e is: two components that compete for a row have |e| of 30 .. 1e4 there, and
-// their responsibilities hang on the difference -- float32 transforms and a float32 e leave
-// ulp(|e|) in it.
+// component_constants of every component, once per call: P [5, C] = s1, s2, rho, q, k.
 __global__ __launch_bounds__(kBlock) void mdn_shared_prep_kernel(
     int C, const float* __restrict__ sig, const float* __restrict__ cor, double* __restrict__ P) {
   const int c = blockIdx.x * kBlock + threadIdx.x;
   if (c >= C) return;
-  const double r1 = sig[2 * c], r2 = sig[2 * c + 1], a = fabs(static_cast<double>(cor[c]));
-  const double s1 = fmax(r1, 0.0) + log1p(exp(-fabs(r1)));
-  const double s2 = fmax(r2, 0.0) + log1p(exp(-fabs(r2)));
-  const double inv1 = 1.0 / (1.0 + a);
-  const double q = (1.0 + 2.0 * a) * (inv1 * inv1);
-  P[c] = s1;
-  P[C + c] = s2;
-  P[2 * C + c] = cor[c] * inv1;
-  P[3 * C + c] = q;
-  P[4 * C + c] = (-1.8378770664093453 - (log(s1) + log(s2))) - 0.5 * log(q);
+  const Component comp = component_constants(sig[2 * c], sig[2 * c + 1], cor[c]);
+  P[c] = comp.s1;
+  P[C + c] = comp.s2;
+  P[2 * C + c] = comp.rho;
+  P[3 * C + c] = comp.q;
+  P[4 * C + c] = comp.k;
 }
 
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-  return v;
+gcg_status launch_prep(int64_t C, const float* sig, const float* cor, double* P, hipStream_t st) {
+  hipLaunchKernelGGL(mdn_shared_prep_kernel, dim3(static_cast<unsigned>((C + kBlock - 1) / kBlock)),
+                     dim3(kBlock), 0, st, static_cast<int>(C), sig, cor, P);
+  GCG_HIP_CHECK(hipGetLastError());
+  return GCG_OK;
 }
 
 // Workgroup g walks the rows [g R, (g + 1) R), wave w of it the rows g R + w (R / 4) ... in
@@ -420,11 +495,9 @@ __global__ __launch_bounds__(kBlock) void mdn_shared_nll_kernel(
     auto e_of = [&](int i) -> double {
       const int c = lane + i * kWave;
       if (c >= C) return -INFINITY;
-      const double rho = P[2 * C + c];
-      const double u1 = static_cast<double>(y1 - mus[2 * c]) / P[c];
-      const double u2 = static_cast<double>(y2 - mus[2 * c + 1]) / P[C + c];
-      const double z = (u1 * u1 + u2 * u2) - 2.0 * rho * (u1 * u2);
-      return ((-0.5 * z) / P[3 * C + c] + P[4 * C + c]) +
+      const Quad<double> t = quad<double>(y1 - mus[2 * c], y2 - mus[2 * c + 1], P[c], P[C + c],
+                                          P[2 * C + c]);  // float32 differences, widened
+      return exponent(t.z, P[3 * C + c], P[4 * C + c]) +
              (static_cast<double>(lg[i] - lp.max) - log_sum_pi);
     };
     double M = -INFINITY;
@@ -450,14 +523,10 @@ __global__ __launch_bounds__(kBlock) void mdn_shared_nll_kernel(
         if (partials != nullptr) {
           const float s1 = static_cast<float>(P[c]), s2 = static_cast<float>(P[C + c]);
           const float rho = static_cast<float>(P[2 * C + c]), q = static_cast<float>(P[3 * C + c]);
-          const float u1 = (y1 - mus[2 * c]) / s1, u2 = (y2 - mus[2 * c + 1]) / s2;
-          const float z = (u1 * u1 + u2 * u2) - 2.0f * rho * (u1 * u2);
-          const float a1 = (u1 - rho * u2) / q, a2 = (u2 - rho * u1) / q;
-          acc[0][i] = acc[0][i] + w * (a1 / s1);
-          acc[1][i] = acc[1][i] + w * (a2 / s2);
-          acc[2][i] = acc[2][i] + w * ((u1 * a1 - 1.0f) / s1);
-          acc[3][i] = acc[3][i] + w * ((u2 * a2 - 1.0f) / s2);
-          acc[4][i] = acc[4][i] + w * ((u1 * u2 + rho * (1.0f - z / q)) / q);
+          const GradTerms<float> de = grad_terms(
+              quad(y1 - mus[2 * c], y2 - mus[2 * c + 1], s1, s2, rho), s1, s2, rho, q);
+#pragma unroll
+          for (int j = 0; j < 5; ++j) acc[j][i] = acc[j][i] + w * de.d[j];
         }
       }
     }
@@ -480,25 +549,13 @@ __global__ __launch_bounds__(kBlock) void mdn_shared_nll_kernel(
   for (int t = threadIdx.x; t < 5 * C; t += kBlock) out[t] = lds[t];
 }
 
-// dparams[j][c] = factor_j(c) * (partial of workgroup 0 + 1 + ... in order): thread per (j, c).
-//   d mus: -s/B; d sigmas_raw: -s/B * sigmoid(raw); d corxy_raw: -s/B / (1 + |raw|)^2
+// finish_partials in float32 with the NLL's leading factor -scale / B.
 __global__ __launch_bounds__(kBlock) void mdn_shared_finish_kernel(
     int64_t B, int C, int groups, const float* __restrict__ partials,
     const float* __restrict__ sig, const float* __restrict__ cor,
     const float* __restrict__ scale_dev, float* __restrict__ dparams) {
-  const int t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= 5 * C) return;
-  float s = 0.0f;
-  for (int g = 0; g < groups; ++g) s = s + partials[static_cast<int64_t>(g) * 5 * C + t];
-  const int j = t / C, c = t - j * C;
   const float up = (scale_dev != nullptr ? *scale_dev : 1.0f) / static_cast<float>(B);
-  float f = -up;
-  if (j == 2 || j == 3) f = f * sigmoid(sig[2 * c + (j - 2)]);
-  if (j == 4) {
-    const Corr k = corr_of(cor[c]);
-    f = f * (k.inv1 * k.inv1);
-  }
-  dparams[t] = f * s;
+  finish_partials<float>(C, groups, partials, sig, cor, -up, dparams);
 }
 
 // Dt[j C + i]: the density of component j at the mean of component i, in mdn_predict_kernel's
@@ -508,16 +565,16 @@ __global__ __launch_bounds__(kBlock) void mdn_shared_density_kernel(
     const float* __restrict__ cor, float* __restrict__ Dt) {
   const int j = blockIdx.x;
   const float s1 = softplus(sig[2 * j]), s2 = softplus(sig[2 * j + 1]);
-  const Corr k = corr_of(cor[j]);
+  const Corr<float> k = corr_of(cor[j]);
   const float qi = 1.0f / k.q;
   const float sh = sqrtf(0.5f * qi);
   const float a1 = sh / s1, a2 = sh / s2;
+  // the weight opens 1 / 2 pi here, mdn_predict_kernel's (pi * 1 / 2 pi): another rounding, kept
   const float wgt = kInv2Pi * ((1.0f / s1) * (1.0f / s2)) * sqrtf(qi);
   const float m1 = mus[2 * j], m2 = mus[2 * j + 1];
   for (int i = threadIdx.x; i < C; i += kBlock) {
     const float v1 = (mus[2 * i] - m1) * a1, v2 = (mus[2 * i + 1] - m2) * a2;
-    const float z = (v1 * v1 + v2 * v2) - 2.0f * k.rho * (v1 * v2);
-    Dt[static_cast<int64_t>(j) * C + i] = wgt * expf(-z);
+    Dt[static_cast<int64_t>(j) * C + i] = wgt * expf(-quad_z(v1, v2, k.rho));
   }
 }
 
@@ -601,36 +658,16 @@ __global__ __launch_bounds__(kBlock) void mdn_shared_predict_kernel(
       const int c = tid + i * kBlock;
       if (c < C) take_better(bs, bi, score[t][i], c);  // ascending c
     }
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1)
-      take_better(bs, bi, __shfl_xor(bs, off), __shfl_xor(bi, off));
-    if (lane == 0) {
-      best_s[t][wave] = bs;
-      best_i[t][wave] = bi;
-    }
+    wave_best(bs, bi, lane, best_s[t][wave], best_i[t][wave]);
   }
   __syncthreads();
   if (tid < rows) {
-    float bs = best_s[tid][0];
-    int bi = best_i[tid][0];
-    for (int w = 1; w < kWavesPerBlock; ++w) take_better(bs, bi, best_s[tid][w], best_i[tid][w]);
-    // every score NaN leaves no winner: component 0, in bounds
-    const int win = (bi >= 0 && bi < C) ? bi : 0;
+    const int win = winner_of(best_s[tid][0], best_i[tid][0], best_s[tid], best_i[tid], C);
     const int64_t r = r0 + tid;
     if (idx != nullptr) idx[r] = win;
     latlon[2 * r] = mus[2 * win];
     latlon[2 * r + 1] = mus[2 * win + 1];
   }
-}
-
-gcg_status check_shared(const char* fn, int64_t B, int64_t C, int64_t ldl) {
-  if (B < 0 || B > INT32_MAX || C < 1 || C > kMaxComp)
-    return fail(GCG_ERR_INVALID_ARG, "%s: bad sizes B=%lld C=%lld (1 <= C <= %d)", fn,
-                static_cast<long long>(B), static_cast<long long>(C), kMaxComp);
-  if (ldl < C)
-    return fail(GCG_ERR_INVALID_ARG, "%s: row stride %lld < C = %lld", fn,
-                static_cast<long long>(ldl), static_cast<long long>(C));
-  return GCG_OK;
 }
 
 // The workspace of gcg_mdn_shared_nll_f32: P [5, C] doubles, the partials [groups, 5, C], B row
@@ -643,51 +680,37 @@ size_t shared_nll_bytes(int64_t B, int64_t C) {
 // The shared-component model's Gaussians as a layer: G[r][c] = the density of component c at the
 // coordinate of row r, and the gradient of the five parameter planes from an upstream dG.
 
-// One (row, component) in double: the exponent e = -0.5 z / q + k and what the five gradient
-// terms are built from. The difference x - mu is formed in double too (two float32 values:
-// exact), so that a parameter's sum over the rows keeps its meaning when an upstream dG of
-// either sign makes the rows cancel -- under the NLL the weights are responsibilities, all
+// One (row, component) in double. The difference x - mu is formed in double too (two float32
+// values: exact), so that a parameter's sum over the rows keeps its meaning when an upstream dG
+// of either sign makes the rows cancel -- under the NLL the weights are responsibilities, all
 // positive, and float32 terms do (mdn_shared_nll_kernel).
-struct BigausTerm {
-  double u1, u2, z, e;
-};
-__device__ __forceinline__ BigausTerm bigaus_term(float x1, float x2, float m1, float m2,
-                                                  double s1, double s2, double rho, double q,
-                                                  double k) {
-  BigausTerm t;
-  t.u1 = (static_cast<double>(x1) - static_cast<double>(m1)) / s1;
-  t.u2 = (static_cast<double>(x2) - static_cast<double>(m2)) / s2;
-  t.z = (t.u1 * t.u1 + t.u2 * t.u2) - 2.0 * rho * (t.u1 * t.u2);
-  t.e = (-0.5 * t.z) / q + k;
-  return t;
+__device__ __forceinline__ Quad<double> bigaus_quad(const float* __restrict__ X, int64_t r,
+                                                    float m1, float m2, const Component& comp) {
+  return quad(static_cast<double>(X[2 * r]) - static_cast<double>(m1),
+              static_cast<double>(X[2 * r + 1]) - static_cast<double>(m2), comp.s1, comp.s2,
+              comp.rho);
 }
 
 constexpr int kLayerRows = 8;  // rows per workgroup of the forward
 
-// Thread t of workgroup (bx, by) owns component c = bx * 256 + t: its constants once, in double
-// and in mdn_shared_prep_kernel's expressions, then the row tiles by, by + gridDim.y, ... of 8
-// rows each. X is a broadcast load, G a coalesced store; a value depends on its row and
-// component alone. exp is double and G is rounded once.
+// Thread t of workgroup (bx, by) owns component c = bx * 256 + t: its component_constants
+// once, then the row tiles by, by + gridDim.y, ... of 8 rows each. X is a broadcast load, G a
+// coalesced store; a value depends on its row and component alone. exp is double and G is
+// rounded once.
 __global__ __launch_bounds__(kBlock) void bigaus_layer_kernel(
     int64_t B, int C, const float* __restrict__ X, const float* __restrict__ mus,
     const float* __restrict__ sig, const float* __restrict__ cor, float* __restrict__ G,
     int64_t ldg) {
   const int c = blockIdx.x * kBlock + threadIdx.x;
   if (c >= C) return;
-  const double r1 = sig[2 * c], r2 = sig[2 * c + 1], a = fabs(static_cast<double>(cor[c]));
-  const double s1 = fmax(r1, 0.0) + log1p(exp(-fabs(r1)));
-  const double s2 = fmax(r2, 0.0) + log1p(exp(-fabs(r2)));
-  const double inv1 = 1.0 / (1.0 + a);
-  const double q = (1.0 + 2.0 * a) * (inv1 * inv1);
-  const double rho = cor[c] * inv1;
-  const double k = (-1.8378770664093453 - (log(s1) + log(s2))) - 0.5 * log(q);
+  const Component comp = component_constants(sig[2 * c], sig[2 * c + 1], cor[c]);
   const float m1 = mus[2 * c], m2 = mus[2 * c + 1];
   for (int64_t r0 = static_cast<int64_t>(blockIdx.y) * kLayerRows; r0 < B;
        r0 += static_cast<int64_t>(gridDim.y) * kLayerRows) {
     const int64_t stop = std::min<int64_t>(r0 + kLayerRows, B);
     for (int64_t r = r0; r < stop; ++r)
-      G[r * ldg + c] = static_cast<float>(
-          exp(bigaus_term(X[2 * r], X[2 * r + 1], m1, m2, s1, s2, rho, q, k).e));
+      G[r * ldg + c] =
+          static_cast<float>(exp(exponent(bigaus_quad(X, r, m1, m2, comp).z, comp.q, comp.k)));
   }
 }
 
@@ -705,50 +728,28 @@ __global__ __launch_bounds__(kBlock) void bigaus_layer_backward_kernel(
   const int64_t r1 = std::min<int64_t>(r0 + R, B);
   double* out = partials + static_cast<int64_t>(blockIdx.x) * 5 * C;
   for (int c = threadIdx.x; c < C; c += kBlock) {
-    const double s1 = P[c], s2 = P[C + c], rho = P[2 * C + c], q = P[3 * C + c];
-    const double k = P[4 * C + c];
+    const Component comp{P[c], P[C + c], P[2 * C + c], P[3 * C + c], P[4 * C + c]};
     const float m1 = mus[2 * c], m2 = mus[2 * c + 1];
-    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0, acc4 = 0.0;
+    double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int64_t r = r0; r < r1; ++r) {
-      const BigausTerm t = bigaus_term(X[2 * r], X[2 * r + 1], m1, m2, s1, s2, rho, q, k);
-      const double w = static_cast<double>(dG[r * lddg + c]) * exp(t.e);
-      const double a1 = (t.u1 - rho * t.u2) / q, a2 = (t.u2 - rho * t.u1) / q;
-      acc0 = acc0 + w * (a1 / s1);
-      acc1 = acc1 + w * (a2 / s2);
-      acc2 = acc2 + w * ((t.u1 * a1 - 1.0) / s1);
-      acc3 = acc3 + w * ((t.u2 * a2 - 1.0) / s2);
-      acc4 = acc4 + w * ((t.u1 * t.u2 + rho * (1.0 - t.z / q)) / q);
+      const Quad<double> t = bigaus_quad(X, r, m1, m2, comp);
+      const double w = static_cast<double>(dG[r * lddg + c]) * exp(exponent(t.z, comp.q, comp.k));
+      const GradTerms<double> de = grad_terms(t, comp.s1, comp.s2, comp.rho, comp.q);
+#pragma unroll
+      for (int j = 0; j < 5; ++j) acc[j] = acc[j] + w * de.d[j];
     }
-    out[c] = acc0;
-    out[C + c] = acc1;
-    out[2 * C + c] = acc2;
-    out[3 * C + c] = acc3;
-    out[4 * C + c] = acc4;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) out[j * C + c] = acc[j];
   }
 }
 
-// dparams[j][c] = float32(factor_j(c) * (partial of workgroup 0 + 1 + ... in order)), the sum and
-// the factor in double: thread per (j, c).
-//   d mus: s; d sigmas_raw: s * sigmoid(raw); d corxy_raw: s / (1 + |raw|)^2
+// finish_partials in double with the layer's leading factor, scale.
 __global__ __launch_bounds__(kBlock) void bigaus_layer_finish_kernel(
     int C, int groups, const double* __restrict__ partials, const float* __restrict__ sig,
     const float* __restrict__ cor, const float* __restrict__ scale_dev,
     float* __restrict__ dparams) {
-  const int t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= 5 * C) return;
-  double s = 0.0;
-  for (int g = 0; g < groups; ++g) s = s + partials[static_cast<int64_t>(g) * 5 * C + t];
-  const int j = t / C, c = t - j * C;
-  double f = scale_dev != nullptr ? static_cast<double>(*scale_dev) : 1.0;
-  if (j == 2 || j == 3) {
-    const double x = sig[2 * c + (j - 2)], e = exp(-fabs(x));
-    f = f * (x >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e));
-  }
-  if (j == 4) {
-    const double inv1 = 1.0 / (1.0 + fabs(static_cast<double>(cor[c])));
-    f = f * (inv1 * inv1);
-  }
-  dparams[t] = static_cast<float>(f * s);
+  finish_partials<double>(C, groups, partials, sig, cor,
+                          scale_dev != nullptr ? static_cast<double>(*scale_dev) : 1.0, dparams);
 }
 
 // The workspace of gcg_bigaus_layer_backward_f32: P [5, C] and the partials [groups, 5, C], doubles.
@@ -765,7 +766,7 @@ gcg_status gcg_mdn_nll_f32(int64_t B, int64_t C, const float* O, int64_t ldo, co
                            float* loss, void* workspace, size_t workspace_bytes,
                            gcg_stream_t stream) {
   const char* fn = "gcg_mdn_nll_f32";
-  if (gcg_status s = check_layout(fn, B, C, ldo)) return s;
+  if (gcg_status s = check_sizes(fn, B, C, ldo, 6)) return s;
   if (dO != nullptr && ldd < 6 * C)
     return fail(GCG_ERR_INVALID_ARG, "%s: gradient row stride %lld < 6 C", fn,
                 static_cast<long long>(ldd));
@@ -798,7 +799,7 @@ gcg_status gcg_mdn_nll_f32(int64_t B, int64_t C, const float* O, int64_t ldo, co
 gcg_status gcg_mdn_unpack_f32(int64_t B, int64_t C, const float* O, int64_t ldo, float* mus,
                               float* sigmas, float* corxy, float* pis, gcg_stream_t stream) {
   const char* fn = "gcg_mdn_unpack_f32";
-  if (gcg_status s = check_layout(fn, B, C, ldo)) return s;
+  if (gcg_status s = check_sizes(fn, B, C, ldo, 6)) return s;
   if (B == 0) return GCG_OK;
   if (O == nullptr || mus == nullptr || sigmas == nullptr || corxy == nullptr || pis == nullptr)
     return fail(GCG_ERR_INVALID_ARG, "%s: NULL operand", fn);
@@ -819,7 +820,7 @@ gcg_status gcg_mdn_unpack_f32(int64_t B, int64_t C, const float* O, int64_t ldo,
 gcg_status gcg_mdn_predict_f32(int64_t B, int64_t C, const float* O, int64_t ldo, int method,
                                int32_t* idx, float* latlon, gcg_stream_t stream) {
   const char* fn = "gcg_mdn_predict_f32";
-  if (gcg_status s = check_layout(fn, B, C, ldo)) return s;
+  if (gcg_status s = check_sizes(fn, B, C, ldo, 6)) return s;
   if (method != 0 && method != 1)
     return fail(GCG_ERR_INVALID_ARG, "%s: method %d is neither 0 (mixture) nor 1 (pi)", fn, method);
   if (B == 0) return GCG_OK;
@@ -836,7 +837,7 @@ gcg_status gcg_mdn_predict_f32(int64_t B, int64_t C, const float* O, int64_t ldo
 
 gcg_status gcg_mdn_shared_nll_f32_workspace_bytes(int64_t B, int64_t C, size_t* bytes) {
   const char* fn = "gcg_mdn_shared_nll_f32_workspace_bytes";
-  if (gcg_status s = check_shared(fn, B, C, C)) return s;
+  if (gcg_status s = check_sizes(fn, B, C, C, 1)) return s;
   if (bytes == nullptr) return fail(GCG_ERR_INVALID_ARG, "%s: NULL bytes", fn);
   *bytes = shared_nll_bytes(B, C);
   return GCG_OK;
@@ -848,7 +849,7 @@ gcg_status gcg_mdn_shared_nll_f32(int64_t B, int64_t C, const float* L, int64_t 
                                   int64_t lddl, float* dparams, float* loss_rows, float* loss,
                                   void* workspace, size_t workspace_bytes, gcg_stream_t stream) {
   const char* fn = "gcg_mdn_shared_nll_f32";
-  if (gcg_status s = check_shared(fn, B, C, ldl)) return s;
+  if (gcg_status s = check_sizes(fn, B, C, ldl, 1)) return s;
   if (dL != nullptr && lddl < C)
     return fail(GCG_ERR_INVALID_ARG, "%s: gradient row stride %lld < C", fn,
                 static_cast<long long>(lddl));
@@ -873,10 +874,7 @@ gcg_status gcg_mdn_shared_nll_f32(int64_t B, int64_t C, const float* L, int64_t 
   float* partials = dparams != nullptr ? base : nullptr;
   float* rows = loss_rows != nullptr ? loss_rows : base + 5 * static_cast<int64_t>(groups) * C;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const unsigned cblocks = static_cast<unsigned>((C + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(mdn_shared_prep_kernel, dim3(cblocks), dim3(kBlock), 0, st, c,
-                     sigmas_raw, corxy_raw, P);
-  GCG_HIP_CHECK(hipGetLastError());
+  if (gcg_status s = launch_prep(C, sigmas_raw, corxy_raw, P, st)) return s;
 #define GCG_MDN_SHARED_NLL(N)                                                                  \
   hipLaunchKernelGGL((mdn_shared_nll_kernel<N>), dim3(groups), dim3(kBlock),                   \
                      sizeof(float) * 5 * static_cast<size_t>(C), st, B, c, R, L, ldl, Y, mus,  \
@@ -898,7 +896,7 @@ gcg_status gcg_mdn_shared_nll_f32(int64_t B, int64_t C, const float* L, int64_t 
 gcg_status gcg_mdn_shared_density_f32(int64_t C, const float* mus, const float* sigmas_raw,
                                       const float* corxy_raw, float* Dt, gcg_stream_t stream) {
   const char* fn = "gcg_mdn_shared_density_f32";
-  if (gcg_status s = check_shared(fn, 0, C, C)) return s;
+  if (gcg_status s = check_sizes(fn, 0, C, C, 1)) return s;
   if (mus == nullptr || sigmas_raw == nullptr || corxy_raw == nullptr || Dt == nullptr)
     return fail(GCG_ERR_INVALID_ARG, "%s: NULL operand", fn);
   if (!aligned(mus, 4) || !aligned(sigmas_raw, 4) || !aligned(corxy_raw, 4) || !aligned(Dt, 4))
@@ -914,7 +912,7 @@ gcg_status gcg_mdn_shared_predict_f32(int64_t B, int64_t C, const float* L, int6
                                       const float* Dt, const float* mus, int method,
                                       int32_t* idx, float* latlon, gcg_stream_t stream) {
   const char* fn = "gcg_mdn_shared_predict_f32";
-  if (gcg_status s = check_shared(fn, B, C, ldl)) return s;
+  if (gcg_status s = check_sizes(fn, B, C, ldl, 1)) return s;
   if (method != 0 && method != 1)
     return fail(GCG_ERR_INVALID_ARG, "%s: method %d is neither 0 (mixture) nor 1 (pi)", fn, method);
   if (B == 0) return GCG_OK;
@@ -942,7 +940,7 @@ gcg_status gcg_bigaus_layer_f32(int64_t B, int64_t C, const float* X, const floa
                                 const float* sigmas_raw, const float* corxy_raw, float* G,
                                 int64_t ldg, gcg_stream_t stream) {
   const char* fn = "gcg_bigaus_layer_f32";
-  if (gcg_status s = check_shared(fn, B, C, ldg)) return s;
+  if (gcg_status s = check_sizes(fn, B, C, ldg, 1)) return s;
   if (B == 0) return GCG_OK;
   if (X == nullptr || mus == nullptr || sigmas_raw == nullptr || corxy_raw == nullptr ||
       G == nullptr)
@@ -962,7 +960,7 @@ gcg_status gcg_bigaus_layer_f32(int64_t B, int64_t C, const float* X, const floa
 
 gcg_status gcg_bigaus_layer_backward_f32_workspace_bytes(int64_t B, int64_t C, size_t* bytes) {
   const char* fn = "gcg_bigaus_layer_backward_f32_workspace_bytes";
-  if (gcg_status s = check_shared(fn, B, C, C)) return s;
+  if (gcg_status s = check_sizes(fn, B, C, C, 1)) return s;
   if (bytes == nullptr) return fail(GCG_ERR_INVALID_ARG, "%s: NULL bytes", fn);
   *bytes = bigaus_backward_bytes(B, C);
   return GCG_OK;
@@ -974,7 +972,7 @@ gcg_status gcg_bigaus_layer_backward_f32(int64_t B, int64_t C, const float* X, c
                                          float* dparams, void* workspace, size_t workspace_bytes,
                                          gcg_stream_t stream) {
   const char* fn = "gcg_bigaus_layer_backward_f32";
-  if (gcg_status s = check_shared(fn, B, C, lddg)) return s;
+  if (gcg_status s = check_sizes(fn, B, C, lddg, 1)) return s;
   if (B == 0) return GCG_OK;
   if (X == nullptr || mus == nullptr || sigmas_raw == nullptr || corxy_raw == nullptr ||
       dG == nullptr || dparams == nullptr)
@@ -992,9 +990,7 @@ gcg_status gcg_bigaus_layer_backward_f32(int64_t B, int64_t C, const float* X, c
   double* P = static_cast<double*>(workspace);
   double* partials = P + kSharedPlanes * C;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(mdn_shared_prep_kernel, dim3(static_cast<unsigned>((C + kBlock - 1) / kBlock)),
-                     dim3(kBlock), 0, st, c, sigmas_raw, corxy_raw, P);
-  GCG_HIP_CHECK(hipGetLastError());
+  if (gcg_status s = launch_prep(C, sigmas_raw, corxy_raw, P, st)) return s;
   hipLaunchKernelGGL(bigaus_layer_backward_kernel, dim3(groups), dim3(kBlock), 0, st, B, c, R, X,
                      mus, P, dG, lddg, partials);
   GCG_HIP_CHECK(hipGetLastError());

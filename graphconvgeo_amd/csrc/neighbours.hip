@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void scale_l1_rows_kernel(
     double sum = 0.0;
     for (int64_t j = lane; j < D; j += kWave)
       sum += fabs(static_cast<double>(x[j]) * scale[j] + offset[j]);
-    for (int m = kWave / 2; m >= 1; m >>= 1) sum += __shfl_xor(sum, m, kWave);
+    sum = wave_sum(sum);
     float* y = out + r * ldo;
     for (int64_t j = lane; j < D; j += kWave) {
       const double v = static_cast<double>(x[j]) * scale[j] + offset[j];

@@ -34,12 +34,6 @@ __device__ __forceinline__ MaxSum wave_merge(MaxSum v) {
   return v;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
-  return v;
-}
-
 // The four columns 4 q .. 4 q + 3 of a row (-inf past N): one 16-B load where the row is 16-B
 // aligned and the quad is whole, four 4-B loads otherwise -- the same values either way.
 __device__ __forceinline__ float4 load_quad(const float* __restrict__ z, int q, int N, bool vec) {

@@ -37,7 +37,7 @@ import ctypes as C
 import torch
 
 from . import ops as _ops  # registers torch.ops.gcg.* (the compiled path)
-from ._native import GCG_ACT_NONE, GCG_ACT_RELU, call, load
+from ._native import GCG_ACT_NONE, GCG_ACT_RELU, call, device_scalar, load
 # _colsum: the bias gradients' column sums (sparse.colsum), under the name this module uses
 from .sparse import _ptr, _require_cuda, _stream_handle, colsum as _colsum, empty_dense
 
@@ -255,8 +255,7 @@ def gemm_tn(A: torch.Tensor, B: torch.Tensor, scale: Optional[torch.Tensor] = No
     if ws is None or ws.numel() * 4 < nb.value:
         ws = torch.empty(max((nb.value + 15) // 16 * 4, 4), dtype=torch.float32, device=A.device)
         _TN_WS[key] = ws
-    if scale is not None:
-        scale = scale.reshape(1).to(torch.float32).contiguous()
+    scale = device_scalar(scale)
     with torch.cuda.device(A.device):
         call("gcg_gemm_tn", R, M, N, _ptr(A), _ld(A), _ptr(B), _ld(B), _ptr(scale),
              _ptr(out), out.stride(0) if M > 1 else N, _math_code(math), int(tile), _ptr(ws),
@@ -629,7 +628,7 @@ class _SoftmaxXent(torch.autograd.Function):
         M, N = logits.shape
         gl = empty_dense(M, N, logits.device)
         dummy = torch.empty(M, dtype=torch.float32, device=logits.device)
-        g = g_loss.reshape(1).to(torch.float32).contiguous()
+        g = device_scalar(g_loss)
         _rows_call(logits, y, 1.0 / ctx.D, g, gl, dummy, None, ctx.row_weight)
         return gl, None, None, None
 
@@ -683,7 +682,7 @@ class _L1L2Penalty(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         g_acc = g if ctx.needs_input_grad[1] else None
-        g = g.reshape(1).to(torch.float32).contiguous()
+        g = device_scalar(g)
         grads = []
         for i, (W, (l1, l2)) in enumerate(zip(ctx.saved_tensors, ctx.coefs)):
             if not ctx.needs_input_grad[2 + i]:

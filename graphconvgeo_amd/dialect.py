@@ -31,14 +31,13 @@ logistic-regression embeddings, get_vocab / get_frequent_words, k > 1024 in knei
 """
 from __future__ import annotations
 
-import ctypes as C
 import json
 from collections import namedtuple
 
 import numpy as np
 import torch
 
-from ._native import call, load
+from ._native import call, load, workspace as _workspace
 from .geo import _ptr, _stream
 
 Pairs = namedtuple("Pairs", "dialects rows pair_ptr pair_word n_missing")
@@ -186,12 +185,6 @@ def _int32_device(a, dev) -> torch.Tensor:
     if torch.is_tensor(a):
         return a.to(dev).to(torch.int32).contiguous()
     return _upload(a.astype(np.int32), dev)
-
-
-def _workspace(fn, dev, *sizes):
-    nbytes = C.c_size_t()
-    call(fn, *sizes, C.byref(nbytes))
-    return torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev), nbytes.value
 
 
 # ---------------------------------------------------------------- the ABI calls (no readback)

@@ -28,19 +28,13 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from ._native import call
+from ._native import call, workspace as _workspace
 from .geo import _coords, _ptr, _stream
 
 Assignment = namedtuple("Assignment", "labels distances inertia changed")
 
 _PP_ERRORS = {1: "fewer distinct points than clusters", 2: "locs holds a non-finite coordinate",
               3: "u must lie in [0, 1)"}
-
-
-def _workspace(fn, dev, *sizes):
-    nbytes = C.c_size_t()
-    call(fn, *sizes, C.byref(nbytes))
-    return torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev), nbytes.value
 
 
 def _n_points(locs, name="locs") -> int:

@@ -22,7 +22,6 @@ include/gcg_spmm.h.
 """
 from __future__ import annotations
 
-import ctypes
 import logging
 from typing import Optional
 
@@ -32,7 +31,7 @@ import torch
 
 from . import dense
 from . import sparse as gs
-from ._native import call
+from ._native import call, device_scalar, workspace, workspace_bytes
 from .layers import _as_tensor, _glorot_uniform
 from .mdn import MAX_COMPONENTS, _check_components, split_dparams
 from .sparse import _ld, _ptr, _stream_handle
@@ -69,9 +68,7 @@ def bigaus_forward(X: torch.Tensor, mus: torch.Tensor, sigmas_raw: torch.Tensor,
 
 
 def bigaus_backward_workspace_bytes(B: int, C: int) -> int:
-    n = ctypes.c_size_t()
-    call("gcg_bigaus_layer_backward_f32_workspace_bytes", B, C, ctypes.byref(n))
-    return n.value
+    return workspace_bytes("gcg_bigaus_layer_backward_f32_workspace_bytes", B, C)
 
 
 def bigaus_backward(X: torch.Tensor, mus: torch.Tensor, sigmas_raw: torch.Tensor,
@@ -91,10 +88,8 @@ def bigaus_backward(X: torch.Tensor, mus: torch.Tensor, sigmas_raw: torch.Tensor
     dparams = torch.empty((5, C), dtype=torch.float32, device=dev)
     if B == 0:
         return dparams.zero_()
-    nbytes = bigaus_backward_workspace_bytes(B, C)
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
-    if scale is not None:
-        scale = scale.reshape(1).to(torch.float32).contiguous()
+    ws, nbytes = workspace("gcg_bigaus_layer_backward_f32_workspace_bytes", dev, B, C)
+    scale = device_scalar(scale)
     with torch.cuda.device(dev):
         call("gcg_bigaus_layer_backward_f32", B, C, _ptr(X), _ptr(mus), _ptr(sigmas_raw),
              _ptr(corxy_raw), _ptr(dG), _ld(dG), _ptr(scale), _ptr(dparams), _ptr(ws), nbytes,
@@ -259,8 +254,7 @@ def xent_csr_forward_backward(logits: torch.Tensor, Y: gs.DeviceCSR,
     out = None
     if want_grad:
         out = logits if in_place else gs.empty_dense(M, N, dev)
-    if scale_dev is not None:
-        scale_dev = scale_dev.reshape(1).to(torch.float32).contiguous()
+    scale_dev = device_scalar(scale_dev)
     with torch.cuda.device(dev):
         call("gcg_softmax_xent_csr_f32", M, N, _ptr(logits), _ld(logits), Y.n_rows,
              _ptr(Y.indptr), _ptr(Y.indices), _ptr(Y.data), _ptr(rows), float(scale),

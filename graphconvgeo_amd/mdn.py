@@ -30,7 +30,6 @@ only the mixture logits [B, C].
 """
 from __future__ import annotations
 
-import ctypes
 import logging
 from typing import Optional
 
@@ -39,7 +38,7 @@ import torch
 
 from . import dense, geo
 from . import sparse as gs
-from ._native import call
+from ._native import call, device_scalar, workspace, workspace_bytes
 from .dropout import DropoutStream, draw_seed, make_spec
 from .layers import _as_tensor, _glorot_uniform
 from .mlp import BatchSegments, plan_segmented_epoch, w1_step
@@ -99,8 +98,7 @@ def nll_forward_backward(O: torch.Tensor, Y: torch.Tensor, want_grad: bool = Tru
     loss = torch.empty((), dtype=torch.float32, device=dev)
     rows = torch.empty(B, dtype=torch.float32, device=dev)  # also the home of the mean's input
     dO = gs.empty_dense(B, 6 * C, dev) if want_grad else None
-    if scale is not None:
-        scale = scale.reshape(1).to(torch.float32).contiguous()
+    scale = device_scalar(scale)
     with torch.cuda.device(dev):
         call("gcg_mdn_nll_f32", B, C, _ptr(O), _ld(O), _ptr(Y), _ptr(scale), _ptr(dO),
              _ld(dO) if dO is not None else 0, _ptr(rows), _ptr(loss), None, 0,
@@ -174,9 +172,7 @@ def _check_components(mus, sigmas_raw, corxy_raw, C: Optional[int] = None, dev=N
 
 
 def shared_nll_workspace_bytes(B: int, C: int) -> int:
-    n = ctypes.c_size_t()
-    call("gcg_mdn_shared_nll_f32_workspace_bytes", B, C, ctypes.byref(n))
-    return n.value
+    return workspace_bytes("gcg_mdn_shared_nll_f32_workspace_bytes", B, C)
 
 
 def shared_nll_forward_backward(L: torch.Tensor, Y: torch.Tensor, mus: torch.Tensor,
@@ -197,10 +193,8 @@ def shared_nll_forward_backward(L: torch.Tensor, Y: torch.Tensor, mus: torch.Ten
     rows = torch.empty(B, dtype=torch.float32, device=dev)
     dL = gs.empty_dense(B, C, dev) if want_grad else None
     dparams = torch.empty((5, C), dtype=torch.float32, device=dev) if want_grad else None
-    nbytes = shared_nll_workspace_bytes(B, C)
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
-    if scale is not None:
-        scale = scale.reshape(1).to(torch.float32).contiguous()
+    ws, nbytes = workspace("gcg_mdn_shared_nll_f32_workspace_bytes", dev, B, C)
+    scale = device_scalar(scale)
     with torch.cuda.device(dev):
         call("gcg_mdn_shared_nll_f32", B, C, _ptr(L), _ld(L), _ptr(Y), _ptr(mus),
              _ptr(sigmas_raw), _ptr(corxy_raw), _ptr(scale), _ptr(dL),
