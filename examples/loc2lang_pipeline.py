@@ -11,7 +11,12 @@
 Three places, each with words of its own and a few that everybody uses; the local words found
 at the end should be the places' own.
 
-    python examples/loc2lang_pipeline.py [--epochs 40] [--init kmeans --ncomp 6]
+--analyses adds the model's own analyses, which never form the n x V probabilities on the host:
+the most local words from the device (NNModel_loc2lang.local_words), and per planted place the
+top-ranked words of region_word_scores over the test rows nearest to it, with the recall of the
+place's own words (region_recall).
+
+    python examples/loc2lang_pipeline.py [--epochs 40] [--init kmeans --ncomp 6] [--analyses]
 """
 from __future__ import annotations
 
@@ -49,6 +54,8 @@ def main():
     ap.add_argument("--init", choices=("kdtree", "kmeans"), default="kdtree",
                     help="where the initial Gaussians come from")
     ap.add_argument("--ncomp", type=int, default=6, help="components of --init kmeans")
+    ap.add_argument("--analyses", action="store_true",
+                    help="also print the device local words and the places' top-ranked words")
     args = ap.parse_args()
     rng = np.random.default_rng(0)
     np.random.seed(0)
@@ -77,6 +84,20 @@ def main():
     words = loc2lang.local_words(clf.predict(grid), k=12)
     local = int((words < OWN * len(PLACES)).sum())
     print("most local words:", words.tolist(), f"({local} of 12 belong to one place)")
+    if args.analyses:
+        print("most local words, on the device:", clf.local_words(grid, k=12).tolist())
+        nearest = np.abs(Xte[:, None, :] - PLACES[None]).sum(axis=-1).argmin(axis=1)
+        group_rows = np.argsort(nearest, kind="stable")
+        group_ptr = np.concatenate([[0], np.cumsum(np.bincount(nearest, minlength=len(PLACES)))])
+        scores = clf.region_word_scores(Xte, group_ptr, group_rows)
+        gold_ptr = OWN * np.arange(len(PLACES) + 1)
+        rec = loc2lang.region_recall(scores, gold_ptr, np.arange(OWN * len(PLACES)),
+                                     fractions=(0.1, 0.25))
+        order = scores.argsort(dim=1, descending=True, stable=True)[:, :OWN].cpu().numpy()
+        for g in range(len(PLACES)):
+            print(f"place {g}: top-ranked words {order[g].tolist()}")
+        print("recall of the places' own words at k =", rec.ks, "->",
+              [round(r, 3) for r in rec.recall], "(oracle", [round(r, 3) for r in rec.oracle], ")")
     return 0 if local >= 10 else 1
 
 

@@ -19,6 +19,7 @@ Product modules (all compute runs in libgcg_spmm.so HIP kernels; no CPU fallback
                "mixture" prediction rule, NNModel_lang2loc (text -> lat/lon) on the GPU
   loc2lang     the location-to-language model (loc2lang.py): the Gaussian layer, softmax
                cross-entropy against sparse soft targets, Adamax, NNModel_loc2lang (lat/lon -> words)
+               and its analyses on the device (local words, word maps, top words, dialect ranking)
   kmeans       get_cluster_centers: k-means++ / Lloyd k-means and the per-cluster statistics that
                start the mixture models' Gaussians, float64 on the GPU
   dialect      the dialect-embedding evaluation (main.py:108-162, 230-281, 364-384): min-max + l1

@@ -100,6 +100,9 @@ SIGNATURES = {
                                            _p, _p, _i64, _p, _p]),
     "gcg_adamax_step_f32": (C.c_int, [_i64, _p, _p, _p, _p, _p, C.c_float, C.c_float, C.c_float,
                                       _p]),
+    # the model's analyses (csrc/vocab_stats.hip): the row log-sum-exp, the per-word column sums
+    "gcg_row_lse_f64": (C.c_int, [_i64, _i64, _p, _i64, _p, _p]),
+    "gcg_softmax_column_stats_f64": (C.c_int, [_i64, _i64, _p, _i64, _p, _p, _p, _p]),
     "gcg_csr_validate": (C.c_int, [_i64, _i64, _i64, _p, _p, _p, _p]),
     "gcg_index_csr": (C.c_int, [_i64, _p, _i64, _p, _p, _p, C.c_size_t, _psz, _p]),
     "gcg_scatter_add_rows_f32": (C.c_int, [_i64, _p, _p, _p, _i64, _i64, _p, _i64, _p]),

@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "row_maxsum.h"
 
 using namespace gcg;
 
@@ -14,43 +15,9 @@ namespace {
 
 constexpr int64_t kMaxCols = int64_t{1} << 24;
 
-// A running (max, sum of exp(x - max)) pair. An empty pair is (-inf, 0).
-struct MaxSum {
-  float m, s;
-};
-
-// The union of two pairs. Symmetric in its arguments bit for bit (max and + commute), so both
-// lanes of a butterfly exchange hold the same result.
-__device__ __forceinline__ MaxSum merge(MaxSum a, MaxSum b) {
-  const float m = fmaxf(a.m, b.m);
-  if (m == -INFINITY) return MaxSum{m, 0.0f};
-  return MaxSum{m, a.s * expf(a.m - m) + b.s * expf(b.m - m)};
-}
-
-__device__ __forceinline__ MaxSum wave_merge(MaxSum v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1)
-    v = merge(v, MaxSum{__shfl_xor(v.m, off), __shfl_xor(v.s, off)});
-  return v;
-}
-
-// The four columns 4 q .. 4 q + 3 of a row (-inf past N): one 16-B load where the row is 16-B
-// aligned and the quad is whole, four 4-B loads otherwise -- the same values either way.
-__device__ __forceinline__ float4 load_quad(const float* __restrict__ z, int q, int N, bool vec) {
-  const int j = 4 * q;
-  if (vec && j + 4 <= N) return *reinterpret_cast<const float4*>(z + j);
-  float4 v;
-  v.x = z[j];  // j < N: the caller's loop bound
-  v.y = j + 1 < N ? z[j + 1] : -INFINITY;
-  v.z = j + 2 < N ? z[j + 2] : -INFINITY;
-  v.w = j + 3 < N ? z[j + 3] : -INFINITY;
-  return v;
-}
-
 // One workgroup of 256 threads per row (rows blockIdx.x, + gridDim.x, ...).
-//   1. thread t folds the quads t, t + 256, ... in order into a MaxSum: the quad's maximum
-//      first (one rescale of the running sum per quad), then its four terms in column order;
-//      the lanes merge by an xor butterfly (32, 16, .. 1), the waves as ((w0 + w1) + w2) + w3.
+//   1. the row's MaxSum (block_row_maxsum, row_maxsum.h): thread t folds the quads t, t + 256,
+//      ... in order, the lanes merge by an xor butterfly, the waves as ((w0 + w1) + w2) + w3.
 //   2. thread t adds the target entries t, t + 256, ... of the row: y (for T) and
 //      y * (lse - z[col]); lanes by the butterfly, waves in order.
 //   3. after a barrier (out may be the logits: every z[col] has been read), out = (s T) * p.
@@ -70,30 +37,7 @@ __global__ __launch_bounds__(kBlock) void softmax_xent_csr_kernel(
   for (int64_t i = blockIdx.x; i < M; i += gridDim.x) {
     const float* z = logits + i * ldl;
     const bool vec = (reinterpret_cast<uintptr_t>(z) & 15) == 0;
-    MaxSum acc{-INFINITY, 0.0f};
-    for (int q = tid; q < quads; q += kBlock) {
-      const float4 v = load_quad(z, q, N, vec);
-      const float qm = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
-      if (qm > acc.m) {
-        acc.s = acc.s * expf(acc.m - qm);
-        acc.m = qm;
-      }
-      if (acc.m != -INFINITY) {
-        acc.s = acc.s + expf(v.x - acc.m);
-        acc.s = acc.s + expf(v.y - acc.m);
-        acc.s = acc.s + expf(v.z - acc.m);
-        acc.s = acc.s + expf(v.w - acc.m);
-      }
-    }
-    acc = wave_merge(acc);
-    if (lane == 0) {
-      red_m[wave] = acc.m;
-      red_s[wave] = acc.s;
-    }
-    __syncthreads();
-    MaxSum row{red_m[0], red_s[0]};
-#pragma unroll
-    for (int w = 1; w < kWavesPerBlock; ++w) row = merge(row, MaxSum{red_m[w], red_s[w]});
+    const MaxSum row = block_row_maxsum(z, N, vec, red_m, red_s);
     const float lse = row.m + logf(row.s);
 
     float T = 1.0f;  // y_indptr NULL: out = softmax

@@ -16,6 +16,15 @@ l1-normalised bag of words by categorical cross-entropy with Adamax (loc2lang.py
                            parameter
   NNModel_loc2lang         the reference's class: constructor arguments, fit, predict
   local_words              get_local_words (loc2lang.py:755-766) without the named-entity filter
+  row_lse                  the float64 log-sum-exp of every logits row  gcg_row_lse_f64
+  softmax_column_stats     per word, sum_n p and sum_n p log p of       gcg_softmax_column_stats_f64
+                           p = softmax(z), accumulated over row chunks
+  region_recall            the recall lines of state_dialect_words (loc2lang.py:587-614) from a
+                           [G, V] score matrix and the regions' gold words
+
+The model's analyses (word_entropies, local_words, word_probabilities, top_words,
+region_word_scores) run on these two kernels in one chunked scan; the n x V probabilities never
+leave the device and are never held whole.
 
 The transforms of the Gaussians' parameters and the order of every sum are stated in
 include/gcg_spmm.h.
@@ -23,6 +32,7 @@ include/gcg_spmm.h.
 from __future__ import annotations
 
 import logging
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
@@ -43,6 +53,8 @@ log = logging.getLogger(__name__)
 MAX_COLS = 1 << 24          # gcg_softmax_xent_csr_f32's widest row
 MAX_HIDDEN = 1024           # the rectify backward's one-pass kernel (sparse.relu_backward)
 EVAL_CHUNK_BYTES = 1 << 30  # a chunk's logits stay under this in evaluation and predict
+
+RegionRecall = namedtuple("RegionRecall", "ks recall oracle per_group ranks")
 
 
 # -- the Gaussian layer ---------------------------------------------------------------------
@@ -309,6 +321,79 @@ def softmax_wide(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> to
     return out
 
 
+# -- the analyses' two passes over a chunk of logits ------------------------------------------------
+def row_lse(logits: torch.Tensor) -> torch.Tensor:
+    """lse [M] float64: max_j z_ij + log sum_j exp(z_ij - max) of every row of logits [M, N]
+    (gcg_row_lse_f64: softmax_xent_csr's float32 fold, the log and the add in double)."""
+    if not isinstance(logits, torch.Tensor):
+        raise TypeError("logits must be a torch tensor")
+    logits = _check_logits(logits)
+    M, N = logits.shape
+    lse = torch.empty(M, dtype=torch.float64, device=logits.device)
+    with torch.cuda.device(logits.device):
+        call("gcg_row_lse_f64", M, N, _ptr(logits), _ld(logits), _ptr(lse),
+             _stream_handle(logits.device))
+    return lse
+
+
+def _check_f64(t, n: int, dev, name: str):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor")
+    gs._require_cuda(t, name)
+    if t.dtype != torch.float64 or t.dim() != 1 or t.numel() != n or t.device != dev or \
+            not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous float64 [{n}] tensor on {dev}")
+
+
+def softmax_column_stats(logits: torch.Tensor, lse: torch.Tensor, S: torch.Tensor,
+                         T: torch.Tensor) -> None:
+    """Adds the rows of logits [M, N] to the per-column sums S, T (float64 [N], zeroed by the
+    caller before the first chunk): with p = exp(z - lse[i]), S[j] += p and T[j] += p (z - lse[i])
+    (0 where p == 0), the rows in ascending order (gcg_softmax_column_stats_f64). Chunks of rows
+    given in order leave the bits of one call over all rows. lse: row_lse(logits)."""
+    if not isinstance(logits, torch.Tensor):
+        raise TypeError("logits must be a torch tensor")
+    logits = _check_logits(logits)
+    M, N = logits.shape
+    _check_f64(lse, M, logits.device, "lse")
+    _check_f64(S, N, logits.device, "S")
+    _check_f64(T, N, logits.device, "T")
+    if S.data_ptr() == T.data_ptr():
+        raise ValueError("S and T must be two tensors")
+    with torch.cuda.device(logits.device):
+        call("gcg_softmax_column_stats_f64", M, N, _ptr(logits), _ld(logits), _ptr(lse), _ptr(S),
+             _ptr(T), _stream_handle(logits.device))
+
+
+def check_words(words, V: int) -> np.ndarray:
+    """Word ids as int64, checked on the host: a 1-D integer array with every id in [0, V);
+    repeats and any order are fine."""
+    words = np.asarray(words)
+    if words.ndim != 1 or (words.size and words.dtype.kind not in "iu"):
+        raise ValueError("words must be a 1-D array of integer word ids")
+    if words.size and (words.min() < 0 or words.max() >= V):
+        raise ValueError(f"words: a word id is outside [0, {V})")
+    return np.ascontiguousarray(words, dtype=np.int64)
+
+
+def check_groups(group_ptr, group_rows, n: int):
+    """(group_ptr, group_rows) as int64, checked on the host: group g holds the rows
+    group_rows[group_ptr[g] : group_ptr[g + 1]]. group_ptr must run monotonically from 0 to
+    len(group_rows), every row id must lie in [0, n), and no group may be empty (its mean does not
+    exist). Groups may overlap."""
+    ptr, rows = np.asarray(group_ptr), np.asarray(group_rows)
+    if ptr.ndim != 1 or ptr.size < 1 or ptr.dtype.kind not in "iu" or rows.ndim != 1 or \
+            (rows.size and rows.dtype.kind not in "iu"):
+        raise ValueError("group_ptr and group_rows must be 1-D integer arrays")
+    if ptr[0] != 0 or ptr[-1] != rows.size or (np.diff(ptr) < 0).any():
+        raise ValueError("group_ptr must be monotone from 0 to len(group_rows)")
+    if (np.diff(ptr) == 0).any():
+        raise ValueError("a group is empty")
+    if rows.size and (rows.min() < 0 or rows.max() >= n):
+        raise ValueError(f"group_rows: a row id is outside [0, {n})")
+    return ptr.astype(np.int64), rows.astype(np.int64)
+
+
 # -- Adamax -------------------------------------------------------------------------------------
 class LasagneAdamax(LasagneOptimizer):
     """lasagne.updates.adamax: t += 1; a_t = lr/(1-b1^t); m = b1*m + (1-b1)*g;
@@ -350,7 +435,10 @@ class NNModel_loc2lang(MiniBatchTrainer):
     sums, gcg_bigaus_layer_backward_f32, one Adamax launch per parameter.
 
     Deviations. The loss is evaluated as sum y (logsumexp - z), finite where the reference's
-    log(softmax) underflows to -inf. Evaluation and predict run in row chunks whose logits stay
+    log(softmax) underflows to -inf; region_word_scores is likewise finite where the reference's
+    np.log(softmax) is -inf (it never forms a probability). top_words ranks the logits, ties to the
+    lower index (the reference argsorts float32 probabilities, to which distinct logits can
+    round, and reverses an unstable sort). Evaluation and predict run in row chunks whose logits stay
     under 1 GiB, the row losses added in row order in float64 (the reference evaluates a split
     in one call). When no epoch satisfies the selection rule (n_epochs = 0, or a NaN loss) the
     last parameters are kept, where the reference would pass None to set_all_param_values and
@@ -587,6 +675,107 @@ class NNModel_loc2lang(MiniBatchTrainer):
         self._built()
         return bigaus_forward(self._to_coords(X), self.mus, self.sigmas, self.corxy).cpu().numpy()
 
+    # -- the analyses (loc2lang.py:516-614, 693-766) ------------------------------------------------
+    def _scan(self, x: torch.Tensor, per_chunk) -> None:
+        """The one pass over the rows of x that every analysis shares: per chunk of _chunk_rows()
+        rows the logits once, their row_lse, then per_chunk(a, b, Z, lse) for the rows [a, b). No
+        host synchronisation; the chunk's logits are dropped before the next chunk's exist."""
+        n, step = x.shape[0], self._chunk_rows()
+        for a in range(0, n, step):
+            b = min(a + step, n)
+            Z = self._logits(x[a:b])
+            per_chunk(a, b, Z, row_lse(Z))
+
+    @torch.no_grad()
+    def word_entropies(self, X) -> torch.Tensor:
+        """float64 [V] on the device: the entropy (natural log, 0 log 0 = 0) of every word's
+        predicted probability over the rows of X after l1-normalising it over those rows -- what
+        get_local_words sorts (loc2lang.py:757-758) -- as log S - T / S from the column sums
+        S = sum_n p, T = sum_n p log p; NaN where S == 0."""
+        self._built()
+        x = self._to_coords(X)
+        S = torch.zeros(self.output_size, dtype=torch.float64, device=self.device)
+        T = torch.zeros_like(S)
+        self._scan(x, lambda a, b, Z, lse: softmax_column_stats(Z, lse, S, T))
+        return torch.where(S == 0, torch.full_like(S, float("nan")), torch.log(S) - T / S)
+
+    def local_words(self, X, k: int = 50) -> np.ndarray:
+        """local_words(self.predict(X), k) without the [n, V] array: the indices of the k lowest
+        word_entropies, ascending, stable."""
+        return torch.argsort(self.word_entropies(X), stable=True)[:int(k)].cpu().numpy()
+
+    @torch.no_grad()
+    def word_probabilities(self, X, words, as_tensor: bool = False):
+        """predict(X)[:, words] as float32 [n, len(words)] (the input of contour_me for the plotted
+        words, loc2lang.py:747-753): the columns gathered from each chunk's own logits,
+        exp(z - lse). words: host word ids in [0, V), any order, repeats allowed. A NumPy array,
+        or the device tensor with as_tensor."""
+        self._built()
+        x = self._to_coords(X)
+        w = torch.from_numpy(check_words(words, self.output_size)).to(self.device)
+        out = torch.empty((x.shape[0], w.numel()), dtype=torch.float32, device=self.device)
+
+        def gather(a, b, Z, lse):
+            out[a:b] = torch.exp(Z[:, w].to(torch.float64) - lse[:, None])
+
+        self._scan(x, gather)
+        return out if as_tensor else out.cpu().numpy()
+
+    @torch.no_grad()
+    def top_words(self, X, k: int) -> np.ndarray:
+        """[n, k] int64: per row of X its k most probable words, the most probable first
+        (np.argsort(preds)[0][::-1][:k], loc2lang.py:701). Ranked on the logits (softmax is
+        monotone), ties to the lower index: a stable descending sort of each chunk in torch."""
+        self._built()
+        k = int(k)
+        if not 1 <= k <= self.output_size:
+            raise ValueError(f"k must be in [1, {self.output_size}]")
+        x = self._to_coords(X)
+        out = torch.empty((x.shape[0], k), dtype=torch.int64, device=self.device)
+
+        def top(a, b, Z, lse):
+            out[a:b] = torch.sort(Z, dim=1, descending=True, stable=True)[1][:, :k]
+
+        self._scan(x, top)
+        return out.cpu().numpy()
+
+    @torch.no_grad()
+    def region_word_scores(self, X, group_ptr, group_rows) -> torch.Tensor:
+        """float32 [G, V] on the device: dialect_normalized_logprobs (loc2lang.py:569-579) of
+        every group of rows of X, mean_{n in g} log p_nv - mean_n log p_nv. The logits are linear
+        in the last hidden layer h, so this is ((mean_g h - mean h) . Wo)_v - (mean_g lse - mean
+        lse): the scan gives lse, _features gives h (the Gaussian layer's output when hid_size is
+        0), the means are taken in float64 and one [G, hid] x [hid, V] GEMM does the rest. Group g
+        holds the rows group_rows[group_ptr[g] : group_ptr[g + 1]] (check_groups); groups may
+        overlap. Finite where the reference's np.log(softmax) underflows to -inf."""
+        self._built()
+        x = self._to_coords(X)
+        n = x.shape[0]
+        if n == 0:
+            raise ValueError("X has no rows")
+        ptr, rows = check_groups(group_ptr, group_rows, n)
+        G = ptr.size - 1
+        # [G + 1, n] float64 weights: row g holds 1 / |g| per member (a row twice counts twice, as
+        # np.mean over the reference's index list would), the last row 1 / n: the global mean
+        A = np.zeros((G + 1, n), np.float64)
+        np.add.at(A, (np.repeat(np.arange(G), np.diff(ptr)), rows), 1.0)
+        A[:G] /= np.diff(ptr)[:, None]
+        A[G] = 1.0 / n
+        A = torch.from_numpy(A).to(self.device)
+        lse = torch.empty(n, dtype=torch.float64, device=self.device)
+
+        def keep(a, b, Z, l):
+            lse[a:b] = l
+
+        self._scan(x, keep)
+        H = self._features(x)[1]
+        means = A @ torch.cat([H.to(torch.float64), lse[:, None]], dim=1)
+        d = means[:G] - means[G]
+        dh = gs.empty_dense(G, H.shape[1], self.device)
+        dh.copy_(d[:, :-1])
+        scores = dense.gemm_nt(dh, self._proj_o.fwd.get(self.Wo, True))
+        return scores.sub_(d[:, -1:].to(torch.float32))
+
     def get_params(self):
         self._built()
         return [p.detach().cpu().numpy() for p in self.params]
@@ -619,3 +808,63 @@ def local_words(preds, k: int = 50) -> np.ndarray:
     ent = -torch.special.xlogy(p, p).sum(dim=0)
     ent = torch.where(norm[0] == 0, torch.full_like(ent, float("nan")), ent)  # entropy of 0 / 0
     return torch.argsort(ent, stable=True)[:int(k)].cpu().numpy()
+
+
+def region_recall(scores, gold_ptr, gold_word,
+                  fractions=(0.01, 0.05, 0.1, 0.15, 0.2)) -> RegionRecall:
+    """The recall lines of state_dialect_words (loc2lang.py:587-614) from scores [G, V] (the
+    model's region_word_scores; any torch tensor or array, on any device) and the regions' gold
+    words: group g's are gold_word[gold_ptr[g] : gold_ptr[g + 1]] (host arrays: ids in [0, V),
+    none twice in a group).
+
+    ks[i] = int(fractions[i] * V), as the reference truncates it (0 for a small V: no word is
+    retrieved). rank(g, w) = #{v : s_gv > s_gw} + #{v > w : s_gv == s_gw}: w's position in
+    reversed(argsort(s_g)) under a stable sort (the reference's argsort is unstable; a NaN score
+    sorts as the largest, as in NumPy). A group's recall at k is the share of its gold words with
+    rank < k; groups without gold words are skipped (covered_dialects) and hold NaN.
+
+    RegionRecall(ks, recall, oracle, per_group, ranks): recall[i] the mean over the remaining
+    groups at ks[i] and oracle[i] the reference's "oracle" line, mean min(k, |gold_g|) / |gold_g|
+    (both NaN when no group has gold words); per_group float64 [len(ks), G]; ranks int64
+    [len(gold_word)]. Plain torch: a sort per covered group, not a hot path."""
+    s = scores if isinstance(scores, torch.Tensor) else torch.as_tensor(np.asarray(scores))
+    if s.dim() != 2:
+        raise ValueError("scores must be [G, V]")
+    G, V = s.shape
+    ptr, words = np.asarray(gold_ptr), np.asarray(gold_word)
+    if ptr.ndim != 1 or ptr.size != G + 1 or ptr.dtype.kind not in "iu" or words.ndim != 1 or \
+            (words.size and words.dtype.kind not in "iu"):
+        raise ValueError(f"gold_ptr must be {G + 1} integers and gold_word a 1-D integer array")
+    if ptr[0] != 0 or ptr[-1] != words.size or (np.diff(ptr) < 0).any():
+        raise ValueError("gold_ptr must be monotone from 0 to len(gold_word)")
+    if words.size and (words.min() < 0 or words.max() >= V):
+        raise ValueError(f"gold_word: a word id is outside [0, {V})")
+    fractions = [float(f) for f in fractions]
+    if any(not 0 <= f <= 1 for f in fractions):
+        raise ValueError("fractions must lie in [0, 1]")
+    ptr, words = ptr.astype(np.int64), words.astype(np.int64)
+    ks = [int(f * V) for f in fractions]
+    ranks = np.zeros(words.size, np.int64)
+    per_group = np.full((len(ks), G), np.nan)
+    oracle = np.full((len(ks), G), np.nan)
+    for g in range(G):
+        w = words[ptr[g]:ptr[g + 1]]
+        if w.size == 0:
+            continue
+        if np.unique(w).size != w.size:
+            raise ValueError(f"gold_word: group {g} holds a word twice")
+        order = torch.argsort(s[g], stable=True)  # ascending; reversed: ties to the higher index
+        place = torch.empty_like(order)
+        place[order] = torch.arange(V, device=s.device)
+        r = (V - 1 - place[torch.as_tensor(w, device=s.device)]).cpu().numpy()
+        ranks[ptr[g]:ptr[g + 1]] = r
+        for i, k in enumerate(ks):
+            per_group[i, g] = float((r < k).sum()) / w.size
+            oracle[i, g] = float(min(k, w.size)) / w.size
+    covered = np.diff(ptr) > 0
+    if covered.any():
+        recall = [float(per_group[i, covered].mean()) for i in range(len(ks))]
+        best = [float(oracle[i, covered].mean()) for i in range(len(ks))]
+    else:
+        recall = best = [float("nan")] * len(ks)
+    return RegionRecall(ks, recall, best, per_group, ranks)

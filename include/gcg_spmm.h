@@ -666,6 +666,41 @@ gcg_status gcg_softmax_xent_csr_f32(int64_t M, int64_t N, const float* logits, i
                                     int64_t ldo, float* loss_rows, gcg_stream_t stream);
 
 /*
+ * What the analyses of the location-to-language model need of a chunk of logits (reference
+ * loc2lang.py:516-614 state_dialect_words, 755-766 get_local_words): the row log-sum-exp and,
+ * per word, two column sums of p = softmax(z). The M x N probabilities are never written.
+ * logits: M x N float32, row stride ldl >= N, 1 <= N <= 2^24; the columns [N, ldl) are never
+ * read. Both calls validate on the host, allocate nothing, use no atomics, and return GCG_OK
+ * without a launch when M == 0.
+ *
+ * gcg_row_lse_f64: lse[i] = max_j z_ij + log sum_j exp(z_ij - max), float64[M]. One workgroup of
+ * 256 threads owns a row and folds it as gcg_softmax_xent_csr_f32's first pass does (the same
+ * code: a float32 running (max, sum) pair per thread over the column quads t, t + 256, ..., the
+ * lanes merged by an xor butterfly, the waves as ((w0 + w1) + w2) + w3; 4-B loads of the same
+ * values where the row is not 16-B aligned); the final log and the final add are in double. A
+ * row's result is a fixed function of its N values: it does not depend on M, the grid, the row's
+ * position or its alignment, and two calls agree bit for bit. A row holding NaN or +inf gives
+ * NaN, a row of -inf gives -inf, and no other row is affected.
+ *
+ * gcg_softmax_column_stats_f64: S and T are float64[N] and are accumulated INTO -- the caller
+ * zeroes them before the first chunk. For every column j, and the rows i = 0 .. M - 1 in
+ * ascending order, with a = double(z_ij) - lse[i] and p = exp(a) in double:
+ *     S[j] = S[j] + p;     T[j] = T[j] + (p > 0 ? p * a : 0)
+ * (a logit of -inf, or an underflow, contributes 0 log 0 = 0, as scipy.stats.entropy counts it).
+ * The entropy of the l1-normalised column is then log S - T / S. A column belongs to one thread
+ * (64 consecutive columns to a wave, one wave per workgroup), which adds the rows one at a time
+ * in row order onto the value it read from S[j] / T[j]: any split of the rows into consecutive
+ * calls leaves S and T bitwise equal to one call over all of them, whatever the chunk size. The
+ * loads of 8 rows are in flight while the previous 8 are added. lse: float64[M], e.g. from
+ * gcg_row_lse_f64 on the same rows; a NaN lse[i] (a non-finite row) makes S NaN in every column.
+ */
+gcg_status gcg_row_lse_f64(int64_t M, int64_t N, const float* logits, int64_t ldl, double* lse,
+                           gcg_stream_t stream);
+gcg_status gcg_softmax_column_stats_f64(int64_t M, int64_t N, const float* logits, int64_t ldl,
+                                        const double* lse, double* S, double* T,
+                                        gcg_stream_t stream);
+
+/*
  * CSR transpose on the device (CSR(X^T) for the X^T . dZ1 gradient of
  * mlpconv.py:71). Output is sorted by (row, col) with stable order for equal
  * entries. out_indptr int32[n_cols+1], out_indices int32[nnz], out_vals f32[nnz].

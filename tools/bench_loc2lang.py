@@ -14,6 +14,15 @@ V = 10,000 / 50,000 / 100,000 words, 64 words per row).
            reference's formulas (forward + backward from a given dG).
   adamax   gcg_adamax_step_f32 on a hid x V weight against the elementwise torch form.
   step     one NNModel_loc2lang training step; host clock per step over an epoch of 10.
+The analyses (n = 4096 coordinates, the logits in the layout the model's GEMM writes):
+  lse      gcg_row_lse_f64 against torch.logsumexp.
+  colstats gcg_softmax_column_stats_f64 against the torch form: softmax, then the two column sums
+           (sum p, sum p log p) in float64. Both kernels' times are also given under the byte
+           model M * N * 4 (one read of the chunk) as a rate, and as a share of 6.3 TB/s.
+  local    model.local_words(X) (the scan: logits, lse, column sums; V numbers come back) against
+           local_words(model.predict(X)) (the n x V probabilities copied to the host, float64
+           torch there); host clock, medians of --steps, the parent path's interquartile range,
+           and whether the device path's median is below the parent's by more than that range.
 Every pair alternates A and B in one process; medians of --steps (>= 20) after --warmup.
 """
 from __future__ import annotations
@@ -32,8 +41,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from graphconvgeo_amd import loc2lang as L  # noqa: E402
+from graphconvgeo_amd import sparse as gs  # noqa: E402
 
 B, C, HID, WORDS = 1000, 500, 500, 64
+N_GRID = 4096       # coordinates of the analyses' rows
+STREAM_GBPS = 6300  # what a streaming kernel achieves on one MI355X
 
 
 def device_ms(fn, calls):
@@ -180,19 +192,91 @@ def bench_step(dev, V, steps, warmup, n_batches=10):
             "steps_per_epoch": n_batches, "ms_per_step": med(times)}
 
 
+def grid_logits(dev, V):
+    """N_GRID x V logits ~ N(0, 1) in empty_dense's layout, as the model's GEMM leaves them."""
+    Z = gs.empty_dense(N_GRID, V, dev)
+    Z.copy_(torch.randn(N_GRID, V, device=dev, generator=torch.Generator(device=dev).manual_seed(5)))
+    return Z
+
+
+def read_once(what, V, d, w):
+    """A kernel that reads the chunk once against its torch form: the times, and the kernel's
+    under the byte model M * N * 4."""
+    model_bytes = N_GRID * V * 4
+    rate = model_bytes / (d[0] * 1e-3) / 1e9
+    return {"what": what, "M": N_GRID, "V": V, "fused_device_ms": d[0], "torch_device_ms": d[1],
+            "fused_wall_ms": w[0], "torch_wall_ms": w[1],
+            "byte_model_MB": round(model_bytes / 1e6, 1),
+            "fused_GBps_of_byte_model": round(rate, 1),
+            "share_of_streaming_rate": round(rate / STREAM_GBPS, 3)}
+
+
+def bench_lse(dev, V, steps, warmup):
+    Z = grid_logits(dev, V)
+
+    def fused():
+        L.row_lse(Z)
+
+    def composed():
+        torch.logsumexp(Z, dim=1)
+
+    d = alternate(fused, composed, steps, warmup, lambda f: device_ms(f, 5))
+    w = alternate(fused, composed, steps, warmup, wall_ms)
+    return read_once("row_lse", V, d, w)
+
+
+def bench_colstats(dev, V, steps, warmup):
+    Z = grid_logits(dev, V)
+    lse = L.row_lse(Z)
+    S = torch.zeros(V, dtype=torch.float64, device=dev)
+    T = torch.zeros_like(S)
+
+    def fused():
+        L.softmax_column_stats(Z, lse, S, T)
+
+    def composed():
+        P = torch.softmax(Z, dim=1).to(torch.float64)
+        P.sum(dim=0), torch.special.xlogy(P, P).sum(dim=0)
+
+    d = alternate(fused, composed, steps, warmup, lambda f: device_ms(f, 3))
+    w = alternate(fused, composed, steps, warmup, wall_ms)
+    return read_once("softmax_column_stats", V, d, w)
+
+
+def bench_local(dev, V, steps, warmup):
+    rng = np.random.default_rng(6)
+    X = np.stack([rng.uniform(25, 49, N_GRID), rng.uniform(-124, -67, N_GRID)],
+                 axis=1).astype(np.float32)
+    np.random.seed(0)
+    clf = L.NNModel_loc2lang(output_size=V, hid_size=HID, n_gaus_comp=C, device=dev)
+    ta, tb = [], []
+    for i in range(warmup + steps):
+        a = wall_ms(lambda: clf.local_words(X))
+        b = wall_ms(lambda: L.local_words(clf.predict(X)))
+        if i >= warmup:
+            ta.append(a)
+            tb.append(b)
+    q1, q3 = np.percentile(tb, [25, 75])
+    return {"what": "local_words", "n": N_GRID, "C": C, "hid": HID, "V": V,
+            "device_wall_ms": med(ta), "predict_then_host_wall_ms": med(tb),
+            "predict_then_host_iqr_ms": round(float(q3 - q1), 4),
+            "device_below_by_more_than_iqr": bool(med(ta) < med(tb) - (q3 - q1))}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--vocab", type=int, nargs="+", default=[10_000, 50_000, 100_000])
-    ap.add_argument("--only", choices=["xent", "layer", "adamax", "step"], nargs="+",
-                    default=["xent", "layer", "adamax", "step"])
+    whats = ["xent", "layer", "adamax", "step", "lse", "colstats", "local"]
+    ap.add_argument("--only", choices=whats, nargs="+", default=whats)
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     if args.steps < 20:
         ap.error("--steps must be at least 20 (medians of 20)")
     dev = torch.device("cuda:0")
-    benches = {"xent": bench_xent, "layer": bench_layer, "adamax": bench_adamax, "step": bench_step}
+    benches = {"xent": bench_xent, "layer": bench_layer, "adamax": bench_adamax, "step": bench_step,
+               "lse": bench_lse, "colstats": bench_colstats, "local": bench_local}
     for what in args.only:
         for V in (args.vocab if what != "layer" else args.vocab[:1]):  # the layer has no V
             line = json.dumps(benches[what](dev, V, args.steps, args.warmup))
