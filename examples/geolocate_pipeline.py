@@ -9,6 +9,10 @@ the graph work and the training on the GPU:
   GPU   --kdtree-bucket N: geo.assign_classes (k-d-tree region labels, data.py:399-421) and
         MLPCONV.geo_eval (mean / median km, Acc@161, tensormain.py:38-54)
 
+  GPU   --device-tfidf: tfidf.dataloader_features (DataLoader.tfidf, data.py:378-397: counting,
+        document frequencies, pruning and weighting in HIP; the host only tokenises) and the
+        device vstack, instead of sklearn's TfidfVectorizer on the host
+
 Synthetic data: users live in one of `regions`; they mention other users mostly from their
 own region and use region-specific words, so the graph and the text both carry the label.
 """
@@ -61,6 +65,9 @@ def main():
     ap.add_argument("--kdtree-bucket", type=int, default=0,
                     help="N > 0: k-d-tree region labels with this bucket size (assignClasses) and "
                          "the geolocation metrics; 0 keeps the stand-in latitude-band labels")
+    ap.add_argument("--device-tfidf", action="store_true",
+                    help="build the TF-IDF features on the GPU (graphconvgeo_amd.tfidf) instead of "
+                         "with sklearn on the host")
     args = ap.parse_args()
     import scipy.sparse as sps
     import torch
@@ -74,11 +81,20 @@ def main():
     H = mention_graph_operator(df_train, df_dev, df_test, celebrity_threshold=args.celebrity,
                                device="cuda")
     t_graph = time.perf_counter() - t0
-    # data.py:378-397 (token pattern drops @mentions; binary tf, l2 norm)
-    vec = TfidfVectorizer(token_pattern=r"(?u)(?<![#@])\b\w\w+\b", binary=True, norm="l2",
-                          min_df=2, max_df=0.5, dtype=np.float32)
-    X = sps.vstack([vec.fit_transform(df_train.text.values), vec.transform(df_dev.text.values),
-                    vec.transform(df_test.text.values)]).tocsr().astype(np.float32)
+    t0 = time.perf_counter()
+    if args.device_tfidf:
+        from graphconvgeo_amd.tfidf import dataloader_features
+
+        X, _ = dataloader_features(df_train, df_dev, df_test, binary=True, norm="l2", min_df=2,
+                                   max_df=0.5, device="cuda")
+        torch.cuda.synchronize()
+    else:
+        # data.py:378-397 (token pattern drops @mentions; binary tf, l2 norm)
+        vec = TfidfVectorizer(token_pattern=r"(?u)(?<![#@])\b\w\w+\b", binary=True, norm="l2",
+                              min_df=2, max_df=0.5, dtype=np.float32)
+        X = sps.vstack([vec.fit_transform(df_train.text.values), vec.transform(df_dev.text.values),
+                        vec.transform(df_test.text.values)]).tocsr().astype(np.float32)
+    t_tfidf = time.perf_counter() - t0
     medians = None
     if args.kdtree_bucket > 0:  # DataLoader.assignClasses on the GPU
         from graphconvgeo_amd.geo import assign_classes
@@ -105,6 +121,8 @@ def main():
            "graph_build_s": round(t_graph, 3), "fit_s": round(t_fit, 3),
            "epochs_run": len(clf.history), "test_acc": round(acc, 4),
            "chance": round(1.0 / regions, 4)}
+    if args.device_tfidf:
+        rec.update(tfidf="device", tfidf_s=round(t_tfidf, 3))
     if medians is not None:
         mean_km, median_km, acc161 = clf.geo_eval("test", locs[2], medians)
         rec.update(classes=int(regions), mean_km=round(mean_km, 3), median_km=round(median_km, 3),

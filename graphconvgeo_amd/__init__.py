@@ -24,6 +24,8 @@ Product modules (all compute runs in libgcg_spmm.so HIP kernels; no CPU fallback
                start the mixture models' Gaussians, float64 on the GPU
   dialect      the dialect-embedding evaluation (main.py:108-162, 230-281, 364-384): min-max + l1
                scaling, the rank of every gold word among all V neighbours, recall@k, kneighbors
+  tfidf        DataLoader.tfidf (data.py:378-397): tokenising on the host, counting, document
+               frequencies, pruning and tf-idf weighting on the GPU, dataloader_features
   synth        seeded synthetic graphs / features for the BASELINE configs
 
 `MLP`, `input_convolution`, `NNModel_lang2loc`, `NNModel_lang2locshared`, `NNModel_loc2lang` and
@@ -42,8 +44,8 @@ __version__ = "0.1.0"
 _os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "8")
 
 __all__ = ["sparse", "ops", "layers", "dense", "distributed", "dist_train", "graph", "mentions",
-           "training", "mlpconv", "mlp", "geo", "mdn", "loc2lang", "dialect", "synth",
-           "MLP",
+           "training", "mlpconv", "mlp", "geo", "mdn", "loc2lang", "dialect", "tfidf",
+           "synth", "MLP",
            "input_convolution",
            "NNModel_lang2loc", "NNModel_lang2locshared", "NNModel_loc2lang", "DeviceCSR"]
 

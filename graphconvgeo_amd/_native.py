@@ -185,6 +185,18 @@ SIGNATURES = {
     "gcg_kneighbors_f32_workspace_bytes": (C.c_int, [_i64, _i64, _i64, _psz]),
     "gcg_kneighbors_f32": (C.c_int, [_i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p,
                                      C.c_size_t, _p]),
+    # TF-IDF features over token ids (csrc/tfidf.hip)
+    "gcg_tfidf_count_workspace_bytes": (C.c_int, [_i64, _i64, _i64, _psz]),
+    "gcg_tfidf_count": (C.c_int, [_i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _p,
+                                  C.c_int32, _p, _p, C.c_size_t, _p]),
+    "gcg_tfidf_select_workspace_bytes": (C.c_int, [_i64, _psz]),
+    "gcg_tfidf_select": (C.c_int, [_i64, _p, _i64, _i64, _p, _p, _p, _p, C.c_size_t, _p]),
+    "gcg_tfidf_idf_f64": (C.c_int, [_i64, _p, _i64, _p, _p]),
+    "gcg_tfidf_compact_workspace_bytes": (C.c_int, [_i64, _psz]),
+    "gcg_tfidf_compact": (C.c_int, [_i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p,
+                                    C.c_size_t, _p]),
+    "gcg_tfidf_weight_f32": (C.c_int, [_i64, _i64, _i64, _p, _p, _p, _p, C.c_int32, C.c_int32,
+                                       C.c_int32, _p, _p]),
     "gcg_spgemm_ex": (C.c_int, [_i64, _i64, _i64, _i64, _p, _p, _p, C.c_int, _i64, _p, _p, _p,
                                 C.c_int, _i64, _p, _p, _p, _p, C.c_int32, _i64, _p]),
 }

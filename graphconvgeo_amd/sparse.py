@@ -553,6 +553,34 @@ class DeviceCSR:
         return f"DeviceCSR(shape={self.shape}, nnz={self.nnz}, device={self.device})"
 
 
+def vstack(parts) -> DeviceCSR:
+    """The parts' rows one below the other (sp.sparse.vstack([X_train, X_dev, X_test]),
+    tensormain.py:215) without a host copy: indices and data concatenated, every part's indptr
+    offset by the entries above it (each part's entry count is already on the host). A part may
+    have no rows; entries keep their order."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("vstack needs at least one part")
+    first = parts[0]
+    for p in parts:
+        if not isinstance(p, DeviceCSR):
+            raise TypeError("vstack takes DeviceCSR parts")
+        if p.n_cols != first.n_cols:
+            raise ValueError(f"parts differ in width: {p.n_cols} != {first.n_cols} columns")
+        if p.device != first.device:
+            raise ValueError("parts live on different devices")
+    nnz = sum(p.nnz for p in parts)
+    n_rows = sum(p.n_rows for p in parts)
+    if nnz >= 2**31 or n_rows >= 2**31 - 1:
+        raise ValueError("stacked CSR too large for int32 indices")
+    ptrs, above = [first.indptr[:1]], 0
+    for p in parts:
+        ptrs.append(p.indptr[1:] + above if above else p.indptr[1:])
+        above += p.nnz
+    return DeviceCSR(torch.cat(ptrs), torch.cat([p.indices for p in parts]),
+                     torch.cat([p.data for p in parts]), (n_rows, first.n_cols), validate=False)
+
+
 def _same_device(t: torch.Tensor, A: "DeviceCSR", name: str):
     if t.device != A.device:
         raise ValueError(f"{name} is on {t.device} but the operator lives on {A.device}")

@@ -23,6 +23,8 @@
  *   data.py:399-419 assignClasses (kdtree.py)   gcg_kdtree_fit_f64, gcg_segment_medians_f64,
  *                                               gcg_class_medians_f64, gcg_nearest_class_f64
  *   tensormain.py:38-54 geo_eval                gcg_geo_eval_f64 (gcg_haversine_km_f64)
+ *   data.py:378-397 DataLoader.tfidf            gcg_tfidf_count, gcg_tfidf_select,
+ *                                               gcg_tfidf_compact, gcg_tfidf_weight_f32
  *
  * Conventions (scipy CSR layout, as `scipy.sparse.csr_matrix` holds it):
  *   indptr  int32[n_rows + 1], indices int32[nnz], vals float32[nnz]; dense operands
@@ -1230,6 +1232,77 @@ gcg_status gcg_kneighbors_f32(int64_t V, int64_t D, const float* E, int64_t lde,
                               const float* queries, int64_t ldq, int64_t k, float* dist2,
                               int32_t* index, int32_t* status_dev, void* workspace,
                               size_t workspace_bytes, gcg_stream_t stream);
+
+/*
+ * TF-IDF features over token ids (DataLoader.tfidf, data.py:378-397: sklearn's TfidfVectorizer at
+ * ngram_range (1, 1), smooth_idf). The host tokenises and owns the term dictionary; these entries
+ * do what is arithmetic over ids. None of them synchronizes or allocates.
+ *
+ * gcg_tfidf_count: one chunk of n_docs whole documents into a canonical count CSR (columns
+ * sorted and unique per row, int32 counts). doc_ptr[0 .. n_docs] (int64) are token offsets, and
+ * `tokens` points at token doc_ptr[0]: the chunk's n_tokens = doc_ptr[n_docs] - doc_ptr[0] ids.
+ * With `rank` (int32[n_terms]) an id t in [0, n_terms) is replaced by rank[t] first (the
+ * lexicographic position of a first-seen id). An id outside [0, n_terms), before or after the
+ * map, is dropped. The keys (document << bits(n_terms)) | term are 64-bit and sorted over their
+ * significant bits only, so n_docs * n_terms may exceed 2^32.
+ *   Chunks append: *nnz_dev holds the entries written so far (set it to 0 before the first
+ * chunk); the chunk's entries go to indices / counts [*nnz_dev ...), indptr[0 .. n_docs]
+ * receives *nnz_dev + the rows' offsets (pass the global indptr + the chunk's first document;
+ * the next chunk rewrites the shared boundary with the same value), and *nnz_dev moves on. A
+ * chunk has at most n_tokens entries, so capacity = the corpus' token count always suffices;
+ * where *nnz_dev + the chunk's entries would exceed `capacity` nothing is written and
+ * *status_dev = GCG_ERR_WORKSPACE (status_dev is only ever set, never cleared). To size exactly
+ * instead, pass indptr = indices = counts = NULL: the call then only moves *nnz_dev on by the
+ * chunk's entry count and leaves df alone.
+ *   df (int64[n_terms], or NULL) accumulates the number of rows that hold each term, by
+ * df_mode 0 = one integer atomic per entry, 1 = from a term-ordered copy of the chunk's columns
+ * (a second, 32-bit sort; one plain add per distinct term). Both are exact.
+ */
+gcg_status gcg_tfidf_count_workspace_bytes(int64_t n_docs, int64_t n_tokens, int64_t n_terms,
+                                           size_t* bytes);
+gcg_status gcg_tfidf_count(int64_t n_docs, int64_t n_terms, int64_t n_tokens,
+                           const int64_t* doc_ptr, const int32_t* tokens, const int32_t* rank,
+                           int32_t* indptr, int32_t* indices, int32_t* counts, int64_t capacity,
+                           int64_t* nnz_dev, int64_t* df, int32_t df_mode, int32_t* status_dev,
+                           void* workspace, size_t workspace_bytes, gcg_stream_t stream);
+/*
+ * Vocabulary pruning (CountVectorizer._limit_features with the bounds already integers): term t
+ * is kept iff lo <= df[t] <= hi. new_id[t] = the number of kept terms below t, or -1;
+ * kept_df[new_id[t]] = df[t] (capacity n_terms); *n_kept_dev = the number kept.
+ * gcg_tfidf_idf_f64: idf[t] = ln((1 + n_docs) / (1 + df[t])) + 1 in float64.
+ */
+gcg_status gcg_tfidf_select_workspace_bytes(int64_t n_terms, size_t* bytes);
+gcg_status gcg_tfidf_select(int64_t n_terms, const int64_t* df, int64_t lo, int64_t hi,
+                            int32_t* new_id, int64_t* kept_df, int64_t* n_kept_dev,
+                            void* workspace, size_t workspace_bytes, gcg_stream_t stream);
+gcg_status gcg_tfidf_idf_f64(int64_t n_terms, const int64_t* df, int64_t n_docs, double* idf,
+                             gcg_stream_t stream);
+/*
+ * Column compaction: the entries of the count CSR whose column has new_id >= 0, relabelled, in
+ * their order; a row may become empty. Two calls: with out_indices = out_counts = NULL the new
+ * out_indptr[0 .. n_rows] is written (out_indptr[n_rows] = the entry count, the capacity the
+ * second call needs; this call uses the workspace); with them the entries are written from
+ * that out_indptr (no workspace). An entry past `capacity` is not written.
+ */
+gcg_status gcg_tfidf_compact_workspace_bytes(int64_t n_rows, size_t* bytes);
+gcg_status gcg_tfidf_compact(int64_t n_rows, int64_t n_terms, int64_t nnz, const int32_t* indptr,
+                             const int32_t* indices, const int32_t* counts, const int32_t* new_id,
+                             int32_t* out_indptr, int32_t* out_indices, int32_t* out_counts,
+                             int64_t capacity, void* workspace, size_t workspace_bytes,
+                             gcg_stream_t stream);
+/*
+ * Counts -> float32 values of the same CSR (TfidfTransformer.transform): tf = 1 if binary else
+ * the count; tf = ln(tf) + 1 if sublinear_tf; tf *= idf[column] if idf != NULL; then the row is
+ * divided by its l2 or l1 norm (norm = GCG_TFIDF_NORM_*); an empty or zero-norm row is left as
+ * it is. All in float64, the row sum in a fixed order without atomics (one wave per row: lane l
+ * folds entries l, l + 64, ... in order, then a butterfly over the lanes), one rounding to
+ * float32 at the store.
+ */
+enum { GCG_TFIDF_NORM_NONE = 0, GCG_TFIDF_NORM_L1 = 1, GCG_TFIDF_NORM_L2 = 2 };
+gcg_status gcg_tfidf_weight_f32(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t* indptr,
+                                const int32_t* indices, const int32_t* counts, const double* idf,
+                                int32_t binary, int32_t sublinear_tf, int32_t norm, float* vals,
+                                gcg_stream_t stream);
 
 #ifdef __cplusplus
 }
