@@ -12,6 +12,9 @@ the graph work and the training on the GPU:
   GPU   --device-tfidf: tfidf.dataloader_features (DataLoader.tfidf, data.py:378-397: counting,
         document frequencies, pruning and weighting in HIP; the host only tokenises) and the
         device vstack, instead of sklearn's TfidfVectorizer on the host
+  GPU   --device-tokenizer (with --device-tfidf): tfidf.tokenize_corpus_device finds the tokens
+        in the UTF-8 bytes and builds the term dictionary in HIP; the host lowers, joins and
+        encodes the corpus and handles each distinct term once
 
 Synthetic data: users live in one of `regions`; they mention other users mostly from their
 own region and use region-specific words, so the graph and the text both carry the label.
@@ -68,7 +71,12 @@ def main():
     ap.add_argument("--device-tfidf", action="store_true",
                     help="build the TF-IDF features on the GPU (graphconvgeo_amd.tfidf) instead of "
                          "with sklearn on the host")
+    ap.add_argument("--device-tokenizer", action="store_true",
+                    help="with --device-tfidf: tokenise on the GPU as well "
+                         "(tfidf.tokenize_corpus_device)")
     args = ap.parse_args()
+    if args.device_tokenizer and not args.device_tfidf:
+        ap.error("--device-tokenizer needs --device-tfidf")
     import scipy.sparse as sps
     import torch
     from sklearn.feature_extraction.text import TfidfVectorizer
@@ -85,8 +93,9 @@ def main():
     if args.device_tfidf:
         from graphconvgeo_amd.tfidf import dataloader_features
 
-        X, _ = dataloader_features(df_train, df_dev, df_test, binary=True, norm="l2", min_df=2,
-                                   max_df=0.5, device="cuda")
+        X, vec = dataloader_features(df_train, df_dev, df_test, binary=True, norm="l2", min_df=2,
+                                     max_df=0.5, device="cuda",
+                                     tokenizer="device" if args.device_tokenizer else "host")
         torch.cuda.synchronize()
     else:
         # data.py:378-397 (token pattern drops @mentions; binary tf, l2 norm)
@@ -122,7 +131,8 @@ def main():
            "epochs_run": len(clf.history), "test_acc": round(acc, 4),
            "chance": round(1.0 / regions, 4)}
     if args.device_tfidf:
-        rec.update(tfidf="device", tfidf_s=round(t_tfidf, 3))
+        rec.update(tfidf="device", tfidf_s=round(t_tfidf, 3), tokenizer=vec.tokenizer,
+                   tokenize_s=round(vec.tokenize_s_, 3))
     if medians is not None:
         mean_km, median_km, acc161 = clf.geo_eval("test", locs[2], medians)
         rec.update(classes=int(regions), mean_km=round(mean_km, 3), median_km=round(median_km, 3),

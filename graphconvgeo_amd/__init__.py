@@ -24,8 +24,9 @@ Product modules (all compute runs in libgcg_spmm.so HIP kernels; no CPU fallback
                start the mixture models' Gaussians, float64 on the GPU
   dialect      the dialect-embedding evaluation (main.py:108-162, 230-281, 364-384): min-max + l1
                scaling, the rank of every gold word among all V neighbours, recall@k, kneighbors
-  tfidf        DataLoader.tfidf (data.py:378-397): tokenising on the host, counting, document
-               frequencies, pruning and tf-idf weighting on the GPU, dataloader_features
+  tfidf        DataLoader.tfidf (data.py:378-397): tokenising on the host or, opt-in, on the GPU
+               (tokenize_corpus_device), counting, document frequencies, pruning and tf-idf
+               weighting on the GPU, dataloader_features
   synth        seeded synthetic graphs / features for the BASELINE configs
 
 `MLP`, `input_convolution`, `NNModel_lang2loc`, `NNModel_lang2locshared`, `NNModel_loc2lang` and

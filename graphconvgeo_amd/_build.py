@@ -20,12 +20,13 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 # soft targets, the k-means initialisation of the Gaussian components, the dialect-embedding
 # evaluation (scaling, neighbour ranks, kneighbors), the row log-sum-exp and per-word column sums
 # of the location-to-language model's analyses, the TF-IDF features over token ids (counting,
-# document frequencies, pruning, weighting), error/version helpers.
+# document frequencies, pruning, weighting), tokenising the corpus for them (marking the tokens
+# in the UTF-8 bytes, the term dictionary), error/version helpers.
 # Compiled in parallel, linked into one shared library.
 SOURCES = [os.path.join(CSRC, f) for f in
            ("spmm.hip", "spmm_bf16.hip", "csr_ops.hip", "graph_build.hip", "spgemm.hip", "dense.hip", "dropout.hip",
             "minibatch.hip", "geo.hip", "kmeans.hip", "mdn.hip", "softmax_csr.hip", "neighbours.hip",
-            "vocab_stats.hip", "tfidf.hip", "errors.cpp")]
+            "vocab_stats.hip", "tfidf.hip", "tokenize.hip", "errors.cpp")]
 INTERNAL_HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "spmm_shared.h", "index_kernels.h",
                                                     "gemm_epilogue.inc", "philox.h",
                                                     "rectify_backward_pass.inc",

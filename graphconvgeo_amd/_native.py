@@ -197,6 +197,15 @@ SIGNATURES = {
                                     C.c_size_t, _p]),
     "gcg_tfidf_weight_f32": (C.c_int, [_i64, _i64, _i64, _p, _p, _p, _p, C.c_int32, C.c_int32,
                                        C.c_int32, _p, _p]),
+    # tokenising the corpus for them (csrc/tokenize.hip)
+    "gcg_tokenize_tile_bytes": (C.c_int32, []),
+    "gcg_tokenize_mark_workspace_bytes": (C.c_int, [_i64, _psz]),
+    "gcg_tokenize_mark": (C.c_int, [_i64, _p, _p, C.c_int32, _p, _p, _p, _p, C.c_size_t, _p]),
+    "gcg_tokenize_terms_workspace_bytes": (C.c_int, [_i64, C.c_int32, _psz]),
+    "gcg_tokenize_terms": (C.c_int, [_i64, _p, _p, _p, _i64, _i64, _p, C.c_int32, _p, _p, _p, _p,
+                                     _p, _p, C.c_size_t, _p]),
+    "gcg_tokenize_remap_workspace_bytes": (C.c_int, [_i64, _psz]),
+    "gcg_tokenize_remap": (C.c_int, [_i64, _p, _i64, _p, _i64, _p, _p, _p, _p, C.c_size_t, _p]),
     "gcg_spgemm_ex": (C.c_int, [_i64, _i64, _i64, _i64, _p, _p, _p, C.c_int, _i64, _p, _p, _p,
                                 C.c_int, _i64, _p, _p, _p, _p, C.c_int32, _i64, _p]),
 }

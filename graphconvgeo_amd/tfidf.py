@@ -11,6 +11,12 @@ one rounding to float32 at the store.
 `DeviceCSR`; `dataloader_features` is DataLoader.tfidf followed by the vstack of
 tensormain.py:215: the X that MLPCONV.fit, MLP.fit, the mixture-density models and loc2lang
 take. Out of scope: n-grams above 1, max_features, strip_accents, smooth_idf=False.
+
+`tokenize_corpus_device` is `tokenize_corpus` with the per-token work on the device
+(csrc/tokenize.hip). The host keeps what Python does in C loops over the whole corpus (lower,
+join, encode) and what is per unique term (slicing the terms' strings out of the bytes, the stop
+list or the fitted vocabulary); the device finds the tokens in the UTF-8 bytes, builds the term
+dictionary in order of first appearance and applies the host's per-term action.
 """
 from __future__ import annotations
 
@@ -18,6 +24,7 @@ import ctypes as C
 import math
 import numbers
 import re
+import time
 
 import numpy as np
 import torch
@@ -27,6 +34,16 @@ from ._native import call
 from .sparse import DeviceCSR, vstack
 
 TOKEN_PATTERN = r"(?u)(?<![#@])\b\w\w+\b"  # data.py:256
+SKLEARN_TOKEN_PATTERN = r"(?u)\b\w\w+\b"  # CountVectorizer's default
+
+# The patterns tokenize_corpus_device restates as a run rule -> whether a run preceded by '#' or
+# '@' is dropped.
+DEVICE_PATTERNS = {TOKEN_PATTERN: 1, SKLEARN_TOKEN_PATTERN: 0}
+# Bytes of text one workgroup marks (GCG_TOKENIZE_TILE_BYTES, csrc/tokenize.hip).
+TOKENIZE_TILE_BYTES = 4096
+TOKENIZERS = ("host", "device")
+_DROP = -2  # GCG_TOKENIZE_DROP
+_N_CODE_POINTS = 0x110000
 
 # Tokens counted per gcg_tfidf_count call: a corpus with more is cut into chunks of whole
 # documents (the sizes come from the host's doc_ptr, so a chunk boundary costs no
@@ -89,6 +106,194 @@ def tokenize_corpus(texts, token_pattern=TOKEN_PATTERN, stop_words="english", lo
     return doc_ptr, np.asarray(tokens, np.int32), None if fixed else list(ids)
 
 
+_word_table = None
+
+
+def word_char_table() -> np.ndarray:
+    """The regex engine's \\w for `str` patterns as a bitmap over U+0000..U+10FFFF: bit cp & 31
+    of uint32 word cp >> 5. Asked of `re` itself, once (every code point as a one-character
+    string, split on non-word characters), not restated."""
+    global _word_table
+    if _word_table is None:
+        word = np.zeros(_N_CODE_POINTS, np.uint8)
+        find = re.compile(r"(?u)\w").finditer
+        step = 1 << 16
+        for lo in range(0, _N_CODE_POINTS, step):
+            # surrogates cannot be encoded and never reach the device: left 0
+            text = "".join(map(chr, range(lo, lo + step)))
+            word[[lo + m.start() for m in find(text)]] = 1
+        table = np.packbits(word, bitorder="little").view("<u4").astype(np.uint32)
+        table.setflags(write=False)
+        _word_table = table
+    return _word_table
+
+
+_table_dev = {}
+
+
+def _word_table_on(dev):
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _table_dev:
+        _table_dev[key] = torch.from_numpy(word_char_table().copy()).to(dev)
+    return _table_dev[key]
+
+
+def _device_pattern(token_pattern) -> int:
+    if token_pattern not in DEVICE_PATTERNS:
+        raise ValueError(f"token_pattern {token_pattern!r} is not one the device tokeniser "
+                         f"restates ({', '.join(map(repr, DEVICE_PATTERNS))}): use tokenize_corpus")
+    return DEVICE_PATTERNS[token_pattern]
+
+
+def _corpus_bytes(texts, lowercase):
+    """(buf, doc_off): the documents, lowercased when asked, joined by one NUL each and encoded
+    to UTF-8. doc_off is None when no document contains a NUL (the separators are then the only
+    NULs and the device finds the documents by them), else the documents' byte offsets."""
+    docs = []
+    for d, text in enumerate(texts):
+        if isinstance(text, bytes):
+            text = text.decode("utf-8")
+        if not isinstance(text, str):
+            raise ValueError(f"document {d} is not a string: {type(text).__name__}")
+        docs.append(text)
+    joined = "\x00".join(docs)
+    plain = joined.count("\x00") == len(docs) - 1
+    # NUL is neither cased nor case-ignorable, so lowering the joined text lowers each document
+    # as on its own, the final-sigma rule included; a document with a NUL of its own is lowered
+    # by itself all the same, since its offsets are taken per document anyway
+    if lowercase and plain:
+        joined = joined.lower()
+    try:
+        if plain:
+            return joined.encode("utf-8"), None
+        parts = [(t.lower() if lowercase else t).encode("utf-8") for t in docs]
+    except UnicodeEncodeError:
+        for d, t in enumerate(docs):
+            try:
+                t.encode("utf-8")
+            except UnicodeEncodeError as e:
+                raise ValueError(f"document {d} cannot be encoded as UTF-8: {e}") from e
+        raise
+    doc_off = np.zeros(len(docs) + 1, np.int64)
+    np.cumsum([len(p) + 1 for p in parts], out=doc_off[1:])
+    return b"\x00".join(parts), doc_off
+
+
+def tokenize_corpus_device(texts, token_pattern=TOKEN_PATTERN, stop_words="english",
+                           lowercase=True, vocabulary=None, device="cuda", hash_bits=64,
+                           timings=None):
+    """tokenize_corpus with the per-token work on the device: (doc_ptr, tokens, terms) under
+    the same contract, `tokens` an int32 device tensor, `doc_ptr` the host int64 array.
+
+    Only the patterns of DEVICE_PATTERNS. The device's term dictionary goes by a 64-bit hash of
+    the token's bytes and is verified byte by byte; where two terms share a hash the corpus is
+    tokenised by tokenize_corpus instead and `tokenize_corpus_device.fallbacks` counts it, so the
+    result is exact either way (`hash_bits` below 64 cuts the hash: for tests). `timings`, a dict,
+    receives the seconds of the stages (prep_s, upload_s, kernels_s, terms_s), each closed by a
+    synchronisation it would not otherwise need."""
+    lookbehind = _device_pattern(token_pattern)
+    stops = _stop_set(stop_words)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("the device tokeniser runs on the GPU: device must be a CUDA (HIP) device")
+    if not 1 <= int(hash_bits) <= 64:
+        raise ValueError("hash_bits must be in 1 .. 64")
+    fixed = vocabulary is not None
+
+    def lap(name, t0):
+        if timings is None:
+            return t0
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        if t0 is not None:
+            timings[name] = timings.get(name, 0.0) + t1 - t0
+        return t1
+
+    t = lap(None, None)
+    texts = list(texts)
+    n_docs = len(texts)
+    buf, doc_off = _corpus_bytes(texts, lowercase)
+    n = len(buf)
+    empty = (np.zeros(n_docs + 1, np.int64), torch.empty(0, dtype=torch.int32, device=dev),
+             None if fixed else [])
+    if n_docs == 0 or n == 0:
+        return empty
+    if n > 1 << 33:
+        raise ValueError("the corpus has more than 2^33 bytes: tokenise it in parts")
+    t = lap("prep_s", t)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    n16 = (n + 15) // 16 * 16
+    tiles = -(-n // TOKENIZE_TILE_BYTES)
+    with torch.cuda.device(dev):
+        table = _word_table_on(dev)
+        text = torch.empty(n16, dtype=torch.uint8, device=dev)
+        # (a bytearray, because torch takes no read-only buffer)
+        text[:n].copy_(torch.frombuffer(bytearray(buf), dtype=torch.uint8))
+        off_dev = None if doc_off is None else torch.from_numpy(doc_off).to(dev)
+        t = lap("upload_s", t)
+        flags = torch.empty(n16, dtype=torch.uint8, device=dev)
+        tile_base = torch.empty(tiles + 1, dtype=torch.int64, device=dev)
+        totals = torch.zeros(2, dtype=torch.int64, device=dev)
+        ws, nbytes = _native.workspace("gcg_tokenize_mark_workspace_bytes", dev, n)
+        call("gcg_tokenize_mark", n, _ptr(text), _ptr(table), lookbehind, _ptr(flags),
+             _ptr(tile_base), _ptr(totals), _ptr(ws), nbytes, stream)
+        n_tokens, n_nul = totals.tolist()
+        if doc_off is None and n_nul != n_docs - 1:
+            raise RuntimeError(f"gcg_tokenize_mark: {n_nul} separators for {n_docs} documents")
+        if n_tokens >= 2**31 - 1:
+            raise ValueError("too many tokens for int32 CSR")
+        if n_tokens == 0:
+            return empty
+        raw_ptr = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+        tok_term = torch.empty(n_tokens, dtype=torch.int32, device=dev)
+        term_start = torch.empty(n_tokens, dtype=torch.int64, device=dev)
+        term_len = torch.empty(n_tokens, dtype=torch.int32, device=dev)
+        result = torch.zeros(2, dtype=torch.int64, device=dev)
+        ws, nbytes = _native.workspace("gcg_tokenize_terms_workspace_bytes", dev, n_tokens,
+                                       int(hash_bits))
+        call("gcg_tokenize_terms", n, _ptr(text), _ptr(flags), _ptr(tile_base), n_tokens, n_docs,
+             _ptr(off_dev), int(hash_bits), _ptr(raw_ptr), _ptr(tok_term), _ptr(term_start),
+             _ptr(term_len), _ptr(result), _ptr(ws), nbytes, stream)
+        n_terms, collision = result.tolist()
+        del ws, flags, tile_base
+        if collision:
+            # two terms under one hash: exact by the host's tokeniser for this corpus
+            tokenize_corpus_device.fallbacks += 1
+            doc_ptr, tokens, terms = tokenize_corpus(texts, token_pattern, stop_words, lowercase,
+                                                     vocabulary)
+            return doc_ptr, torch.from_numpy(tokens).to(dev), terms
+        starts = term_start[:n_terms].cpu().numpy()
+        lens = term_len[:n_terms].cpu().numpy()
+        t = lap("kernels_s", t)
+        # per unique term, never per token: its string, then the stop list or the vocabulary
+        names = [buf[s:e].decode("utf-8") for s, e in zip(starts.tolist(), (starts + lens).tolist())]
+        if fixed:
+            get = vocabulary.get
+            keep = np.fromiter((w not in stops for w in names), bool, n_terms)
+            cols = np.fromiter((get(w, -1) for w in names), np.int64, n_terms)
+            if np.any(keep & ((cols < -1) | (cols >= 2**31))):
+                raise ValueError("vocabulary columns must be in [0, 2^31)")
+            action = np.where(keep, cols, _DROP)
+            terms = None
+        else:
+            keep = np.fromiter((w not in stops for w in names), bool, n_terms)
+            action = np.where(keep, np.cumsum(keep) - 1, _DROP)
+            terms = [w for w, k in zip(names, keep.tolist()) if k]
+        action_dev = torch.from_numpy(action.astype(np.int32)).to(dev)
+        t = lap("terms_s", t)
+        tokens = torch.empty(n_tokens, dtype=torch.int32, device=dev)
+        ptr_dev = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+        ws, nbytes = _native.workspace("gcg_tokenize_remap_workspace_bytes", dev, n_tokens)
+        call("gcg_tokenize_remap", n_tokens, _ptr(tok_term), n_terms, _ptr(action_dev), n_docs,
+             _ptr(raw_ptr), _ptr(tokens), _ptr(ptr_dev), _ptr(ws), nbytes, stream)
+        doc_ptr = ptr_dev.cpu().numpy()
+        lap("kernels_s", t)
+    return doc_ptr, tokens[:int(doc_ptr[-1])], terms
+
+
+tokenize_corpus_device.fallbacks = 0
+
+
 def term_ranks(terms) -> np.ndarray:
     """rank[i] = position of terms[i] among the sorted terms (CountVectorizer._sort_features):
     one sort of the vocabulary; the device applies it to the tokens."""
@@ -142,7 +347,8 @@ def _host_doc_ptr(doc_ptr) -> np.ndarray:
 class TfidfFeatures:
     """TfidfVectorizer(ngram_range=(1, 1), dtype float32) of data.py:387-390 on the GPU.
 
-    fit_transform / transform take texts and return a DeviceCSR; fit_transform_tokens /
+    fit_transform / transform take texts and return a DeviceCSR (tokenizer="host" tokenises
+    with tokenize_corpus, "device" with tokenize_corpus_device); fit_transform_tokens /
     transform_tokens take what tokenize_corpus returns (the token array may already be a device
     tensor). After a fit: vocabulary_ (term -> column) and feature_names_ (sorted), both built
     on first use, n_features_, df_ (int64 device tensor, the kept terms' document frequencies),
@@ -150,9 +356,15 @@ class TfidfFeatures:
 
     def __init__(self, min_df=10, max_df=0.2, norm="l2", use_idf=True, binary=True,
                  sublinear_tf=False, token_pattern=TOKEN_PATTERN, stop_words="english",
-                 device="cuda"):
+                 device="cuda", tokenizer="host"):
         if norm not in _NORMS:
             raise ValueError(f"norm must be 'l2', 'l1' or None, not {norm!r}")
+        if tokenizer not in TOKENIZERS:
+            raise ValueError(f"tokenizer must be 'host' or 'device', not {tokenizer!r}")
+        if tokenizer == "device":
+            _device_pattern(token_pattern)
+        self.tokenizer = tokenizer
+        self.tokenize_s_ = 0.0
         self.min_df, self.max_df, self.norm = min_df, max_df, norm
         self.use_idf, self.binary, self.sublinear_tf = bool(use_idf), bool(binary), bool(sublinear_tf)
         self.token_pattern, self.stop_words = token_pattern, stop_words
@@ -181,8 +393,20 @@ class TfidfFeatures:
         return self._vocabulary
 
     # -- texts ------------------------------------------------------------------------------
+    def _tokenize(self, texts, vocabulary=None):
+        """The chosen tokeniser; tokenize_s_ adds up the seconds spent in it (the device
+        tokeniser ends on a readback, so they are whole)."""
+        t0 = time.perf_counter()
+        if self.tokenizer == "device":
+            out = tokenize_corpus_device(texts, self.token_pattern, self.stop_words,
+                                         vocabulary=vocabulary, device=self.device)
+        else:
+            out = tokenize_corpus(texts, self.token_pattern, self.stop_words, vocabulary=vocabulary)
+        self.tokenize_s_ += time.perf_counter() - t0
+        return out
+
     def fit_transform(self, texts) -> DeviceCSR:
-        doc_ptr, tokens, terms = tokenize_corpus(texts, self.token_pattern, self.stop_words)
+        doc_ptr, tokens, terms = self._tokenize(texts)
         return self.fit_transform_tokens(doc_ptr, tokens, terms)
 
     def fit(self, texts) -> "TfidfFeatures":
@@ -191,8 +415,7 @@ class TfidfFeatures:
 
     def transform(self, texts) -> DeviceCSR:
         self._require_fit()
-        doc_ptr, tokens, _ = tokenize_corpus(texts, self.token_pattern, self.stop_words,
-                                             vocabulary=self.vocabulary_)
+        doc_ptr, tokens, _ = self._tokenize(texts, self.vocabulary_)
         return self.transform_tokens(doc_ptr, tokens)
 
     # -- token ids --------------------------------------------------------------------------

@@ -1304,6 +1304,62 @@ gcg_status gcg_tfidf_weight_f32(int64_t n_rows, int64_t n_cols, int64_t nnz, con
                                 int32_t binary, int32_t sublinear_tf, int32_t norm, float* vals,
                                 gcg_stream_t stream);
 
+/*
+ * Tokenising a corpus on the device (csrc/tokenize.hip): sklearn's analyzer at ngram_range
+ * (1, 1) for the token patterns (?u)\b\w\w+\b (lookbehind = 0) and (?u)(?<![#@])\b\w\w+\b
+ * (lookbehind = 1) over UTF-8 bytes. A token is a maximal run of word characters of at least two
+ * code points; with the lookbehind a run preceded by '#' or '@' is dropped whole. `text` is the
+ * documents (lowercased by the caller where wanted) joined by one NUL byte each: n_bytes bytes,
+ * 16-byte aligned and readable up to n_bytes rounded up to 16 (what lies past n_bytes is not
+ * looked at), at most 2^33. `word_table` is the word class as a bitmap over the code points
+ * U+0000 .. U+10FFFF (bit cp & 31 of word cp >> 5; 34816 words), taken from the regex engine
+ * whose findall is to be matched. Integers only: the outputs are the same on every run. None
+ * of the entries synchronizes or allocates; sizes the host needs are read from the *_dev outputs.
+ *
+ * gcg_tokenize_mark: flags[0 .. round16(n_bytes)) (16-byte aligned) per byte, tile_base
+ * [0 .. tiles] with tiles = ceil(n_bytes / GCG_TOKENIZE_TILE_BYTES) (the tiles' running counts),
+ * totals_dev[0] = the number of tokens, totals_dev[1] = the number of NUL bytes (n_docs - 1
+ * unless a document contains one).
+ *
+ * gcg_tokenize_terms: the term dictionary of the n_tokens tokens marked. Each token's bytes
+ * are hashed to 64 bits, cut to the low hash_bits (1 .. 64; less than 64 is for tests), the
+ * hashes sorted stably with the token index, and every token is compared byte by byte with the
+ * first token of its run, so the result is exact whatever the hash does: tokens with different
+ * bytes under one hash set result_dev[1] = 1 and the caller discards the outputs. Otherwise
+ * tok_term[t] (int32[n_tokens]) = token t's term, the terms numbered in order of first
+ * appearance; term_start / term_len (capacity n_tokens) = byte offset and byte length of each
+ * term's first occurrence; result_dev[0] = the number of terms. doc_ptr[0 .. n_docs] = the
+ * documents' token offsets: with doc_off = NULL the documents are what the NULs separate (the
+ * caller has checked totals_dev[1] = n_docs - 1), else document d starts at byte doc_off[d]
+ * (int64[n_docs + 1], doc_off[n_docs] = n_bytes + 1), which is exact for documents that contain
+ * NUL. n_docs >= 1.
+ *
+ * gcg_tokenize_remap: the caller's action per term (int32[n_terms]): GCG_TOKENIZE_DROP removes
+ * the term's tokens (a stop word), any other value replaces the token (-1, or a column).
+ * tokens (capacity n_tokens) receives the kept tokens in order, doc_ptr[0 .. n_docs] the
+ * documents' offsets among them (doc_ptr[n_docs] = the number kept).
+ */
+#define GCG_TOKENIZE_TILE_BYTES 4096
+#define GCG_TOKENIZE_DROP (-2)
+int32_t gcg_tokenize_tile_bytes(void);
+gcg_status gcg_tokenize_mark_workspace_bytes(int64_t n_bytes, size_t* bytes);
+gcg_status gcg_tokenize_mark(int64_t n_bytes, const uint8_t* text, const uint32_t* word_table,
+                             int32_t lookbehind, uint8_t* flags, uint64_t* tile_base,
+                             int64_t* totals_dev, void* workspace, size_t workspace_bytes,
+                             gcg_stream_t stream);
+gcg_status gcg_tokenize_terms_workspace_bytes(int64_t n_tokens, int32_t hash_bits, size_t* bytes);
+gcg_status gcg_tokenize_terms(int64_t n_bytes, const uint8_t* text, const uint8_t* flags,
+                              const uint64_t* tile_base, int64_t n_tokens, int64_t n_docs,
+                              const int64_t* doc_off, int32_t hash_bits, int64_t* doc_ptr,
+                              int32_t* tok_term, int64_t* term_start, int32_t* term_len,
+                              int64_t* result_dev, void* workspace, size_t workspace_bytes,
+                              gcg_stream_t stream);
+gcg_status gcg_tokenize_remap_workspace_bytes(int64_t n_tokens, size_t* bytes);
+gcg_status gcg_tokenize_remap(int64_t n_tokens, const int32_t* tok_term, int64_t n_terms,
+                              const int32_t* action, int64_t n_docs, const int64_t* doc_ptr_in,
+                              int32_t* tokens, int64_t* doc_ptr, void* workspace,
+                              size_t workspace_bytes, gcg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,19 @@ Per size, one JSON line with
   tokenise_host_s        tokenize_corpus on a sample of joined documents, scaled to the corpus: what
                          the host spends before the device sees a token
 --profile-once runs one fit and exits (for a kernel trace in a run of its own).
+
+--tokenise adds a second line per size, {"op": "tokenise", ...}: the corpus as texts (the token
+ids written out as their terms, 8 bytes each; --multibyte-share S renames that share of the terms
+to start with a 2- or 3-byte character), tokenised by
+  host_s                 tokenize_corpus on a sample of the documents, scaled to the corpus (the
+                         host tokeniser is linear in the documents; the whole corpus takes minutes)
+  device_s               tokenize_corpus_device on the whole corpus, wall time, median of --reps
+  device_split_s         one more run with a synchronisation after each stage: prep_s (lower, join,
+                         encode), upload_s, kernels_s (mark, spans, hash, sort, verify, number,
+                         remap and their readbacks), terms_s (the distinct terms' strings, the stop
+                         list, the action array)
+  equal_on_sample        the device's (doc_ptr, tokens, terms) on the sample equal the host's
+--tokenise-only skips the fits. --profile-once with --tokenise runs one warmed tokenisation.
 """
 from __future__ import annotations
 
@@ -127,6 +140,89 @@ def tokenise_share(terms, tokens, per_doc, n_docs, sample=20_000):
     return (time.perf_counter() - t0) * n_docs / sample
 
 
+_B36 = np.frombuffer(b"0123456789abcdefghijklmnopqrstuvwxyz", np.uint8)
+
+
+def term_bytes(n_terms, multibyte_share, seed=78):
+    """uint8 [n_terms, 9]: term i as 8 bytes of UTF-8 and a space. 'w' and 7 base-36 digits of
+    i, or for a `multibyte_share` of the terms (drawn at random) a 2-byte letter and 6 digits or
+    a 3-byte letter and 5: every term as many bytes, so the corpus is one gather."""
+    ids = np.arange(n_terms, dtype=np.int64)
+    digits = np.stack([_B36[(ids // 36 ** k) % 36] for k in range(6, -1, -1)], 1)
+    out = np.full((n_terms, 9), ord(" "), np.uint8)
+    out[:, 0] = ord("w")
+    out[:, 1:8] = digits
+    kind = np.zeros(n_terms, np.int8)
+    multi = np.random.default_rng(seed).random(n_terms) < multibyte_share
+    kind[multi] = 1 + (ids[multi] % 2)
+    for k, lead in ((1, "\u00e9".encode()), (2, "\u65e5".encode())):   # e-acute, a CJK letter
+        assert 36 ** (7 - k) >= n_terms
+        out[kind == k, :len(lead)] = np.frombuffer(lead, np.uint8)
+    return out
+
+
+def text_corpus(tokens_host, per_doc, table, first=0, count=None):
+    """The documents first .. first + count as str, from the token ids and term_bytes."""
+    n_docs = tokens_host.size // per_doc
+    count = n_docs - first if count is None else count
+    docs, step = [], 1 << 16
+    for d in range(first, first + count, step):
+        e = min(d + step, first + count)
+        rows = table[tokens_host[d * per_doc:e * per_doc]].reshape(e - d, per_doc * 9)
+        docs.extend(bytes(r).decode("utf-8") for r in rows)
+    return docs
+
+
+def same_tokens(a, b):
+    return bool(np.array_equal(a[0], b[0]) and a[2] == b[2] and
+                np.array_equal(torch.as_tensor(a[1]).cpu().numpy(), torch.as_tensor(b[1]).cpu().numpy()))
+
+
+def run_tokenise(name, dev, reps, multibyte_share, sample=20_000):
+    n_docs, per_doc, V = SIZES[name]
+    _, tokens, _ = corpus(n_docs, per_doc, V, dev)
+    tokens_host = tokens.cpu().numpy()
+    del tokens
+    table = term_bytes(V, multibyte_share)
+    docs = text_corpus(tokens_host, per_doc, table)
+    rec = {"op": "tokenise", "config": name, "documents": n_docs, "tokens": int(tokens_host.size),
+           "raw_terms": V, "multibyte_share": multibyte_share,
+           "text_bytes": n_docs * per_doc * 9 + n_docs - 1}
+    part = docs[:sample]
+    tfidf.tokenize_corpus(part[:10])  # the stop list's import is not tokenising
+    t0 = time.perf_counter()
+    want = tfidf.tokenize_corpus(part)
+    rec["host_s"] = round((time.perf_counter() - t0) * n_docs / sample, 2)
+    rec["host_sample_documents"] = sample
+    rec["equal_on_sample"] = same_tokens(tfidf.tokenize_corpus_device(part, device=dev), want)
+    out = {}
+    ms, all_ms = timed(lambda: out.__setitem__("r", tfidf.tokenize_corpus_device(docs, device=dev)),
+                       reps)
+    rec.update(device_s=round(ms * 1e-3, 3), device_all_s=[round(t * 1e-3, 3) for t in all_ms])
+    split = {}
+    allocs = torch.cuda.memory_stats(dev).get("num_device_alloc", 0)
+    tfidf.tokenize_corpus_device(docs, device=dev, timings=split)
+    rec["device_split_s"] = {k: round(v, 3) for k, v in split.items()}
+    # allocations the caching allocator passed on to the driver during that run (they are slow)
+    rec["device_split_driver_allocs"] = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - allocs
+    doc_ptr, toks, terms = out["r"]
+    rec.update(kept_tokens=int(doc_ptr[-1]), terms=len(terms),
+               fallbacks=tfidf.tokenize_corpus_device.fallbacks)
+    # the device's ids are the corpus' own terms in order of first appearance
+    first_seen = np.unique(tokens_host, return_index=True)
+    order = first_seen[0][np.argsort(first_seen[1], kind="stable")]
+    rec["terms_equal_corpus"] = bool(
+        len(terms) == order.size and
+        terms == [bytes(r[:8]).decode("utf-8") for r in table[order]])
+    t0 = time.perf_counter()
+    vec = tfidf.TfidfFeatures(device=dev, tokenizer="device", **DEFAULTS)
+    X = vec.fit_transform(docs)
+    torch.cuda.synchronize()
+    rec.update(fit_transform_texts_s=round(time.perf_counter() - t0, 3),
+               fit_transform_tokenize_s=round(vec.tokenize_s_, 3), features=X.shape[1])
+    print(json.dumps(rec), flush=True)
+
+
 def run(name, dev, host: bool, reps: int):
     n_docs, per_doc, V = SIZES[name]
     doc_ptr, tokens, terms = corpus(n_docs, per_doc, V, dev)
@@ -191,12 +287,26 @@ def main():
     ap.add_argument("--no-host", action="store_true", help="skip the scipy / sklearn baseline")
     ap.add_argument("--df-mode", default=DEFAULT_DF_MODE, choices=sorted(tfidf.DF_MODES),
                     help="--profile-once: how the traced fit accumulates document frequencies")
+    ap.add_argument("--tokenise", action="store_true",
+                    help="also time tokenising the corpus as texts, host against device")
+    ap.add_argument("--tokenise-only", action="store_true", help="--tokenise without the fits")
+    ap.add_argument("--multibyte-share", type=float, default=0.0,
+                    help="--tokenise: the share of the terms that start with a 2- or 3-byte "
+                         "character (the rest are ASCII)")
     ap.add_argument("--profile-once", action="store_true",
                     help="one warmed fit of the first size and nothing else (for a kernel trace)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_tfidf needs the GPU: there is no host path to time")
     dev = torch.device("cuda")
+    if args.profile_once and (args.tokenise or args.tokenise_only):
+        n_docs, per_doc, V = SIZES[args.sizes.split(",")[0]]
+        tokens_host = corpus(n_docs, per_doc, V, dev)[1].cpu().numpy()
+        docs = text_corpus(tokens_host, per_doc, term_bytes(V, args.multibyte_share))
+        for _ in range(2):
+            tfidf.tokenize_corpus_device(docs, device=dev)
+        torch.cuda.synchronize()
+        return
     if args.profile_once:
         tfidf.DF_MODE = args.df_mode
         n_docs, per_doc, V = SIZES[args.sizes.split(",")[0]]
@@ -208,7 +318,10 @@ def main():
         torch.cuda.synchronize()
         return
     for name in args.sizes.split(","):
-        run(name, dev, not args.no_host, args.reps)
+        if not args.tokenise_only:
+            run(name, dev, not args.no_host, args.reps)
+        if args.tokenise or args.tokenise_only:
+            run_tokenise(name, dev, args.reps, args.multibyte_share)
 
 
 if __name__ == "__main__":
