@@ -27,7 +27,8 @@ SOURCES = [os.path.join(CSRC, f) for f in
            ("spmm.hip", "spmm_bf16.hip", "csr_ops.hip", "graph_build.hip", "spgemm.hip", "dense.hip", "dropout.hip",
             "minibatch.hip", "geo.hip", "kmeans.hip", "mdn.hip", "softmax_csr.hip", "neighbours.hip",
             "vocab_stats.hip", "tfidf.hip", "tokenize.hip", "errors.cpp")]
-INTERNAL_HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "spmm_shared.h", "index_kernels.h",
+INTERNAL_HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "layout.h", "scratch.h",
+                                                    "spmm_shared.h", "index_kernels.h",
                                                     "gemm_epilogue.inc", "philox.h",
                                                     "rectify_backward_pass.inc",
                                                     "segment_kernels.h", "row_maxsum.h")]

@@ -8,6 +8,7 @@
 #include <cstdlib>
 
 #include "../../include/gcg_spmm.h"
+#include "layout.h"
 
 namespace gcg {
 
@@ -29,12 +30,6 @@ inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_
 inline int grid_for(int64_t n) {
   int64_t g = (n + 255) / 256;
   return static_cast<int>(std::min<int64_t>(std::max<int64_t>(g, 1), 4096));
-}
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-inline int bits_for(int64_t n) {
-  int b = 1;
-  while (b < 31 && (int64_t{1} << b) < n) ++b;
-  return b;
 }
 
 namespace {  // small device helpers, one copy per translation unit

@@ -5,7 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include "common.h"
+#include "scratch.h"
 #include "index_kernels.h"
 #include "philox.h"
 
@@ -77,21 +77,36 @@ __global__ void permute_transpose_kernel(int64_t nnz, const int32_t* __restrict_
   }
 }
 
-// Stable sort of int32 keys carrying int32 values (iota) -> sorted keys + permutation.
-// Workspace layout: [keys_out n][vals_in n][vals_out n][cub temp].
-gcg_status sort_pairs_ws(int64_t n, int end_bit, size_t* temp_bytes) {
-  uint32_t* dk = nullptr;
-  int32_t* dv = nullptr;
-  size_t tb = 0;
-  hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dk, dv, dv,
-                                                    static_cast<int>(n), 0, end_bit);
-  if (e != hipSuccess) return fail(GCG_ERR_HIP, "SortPairs sizing: %s", hipGetErrorString(e));
-  *temp_bytes = tb;
-  return GCG_OK;
+// The scratch of a stable sort of n int32 keys that carry their positions (iota): the sorted
+// keys, the positions, then `extra` more arrays of n for the caller, hipcub's temporary. The
+// sorted positions go to the caller's `perm`. take_exact: nothing to sort, empty arrays.
+struct SortSpace {
+  int32_t *keys_out, *iota, *extra[2];
+  Tmp tmp;
+  size_t total;
+};
+
+gcg_status sort_space(const char* fn, int64_t n, int end_bit, int extra, void* workspace,
+                      SortSpace* s) {
+  Carver cv(workspace);
+  s->keys_out = cv.take_exact<int32_t>(n);
+  s->iota = cv.take_exact<int32_t>(n);
+  for (int i = 0; i < extra; ++i) s->extra[i] = cv.take_exact<int32_t>(n);
+  auto* k = reinterpret_cast<uint32_t*>(s->keys_out);
+  TmpSize ts;
+  ts.add(GCG_CUB(DeviceRadixSort::SortPairs, k, k, s->iota, s->iota, static_cast<int>(n), 0, end_bit));
+  return ts.take_exact(fn, cv, &s->tmp, &s->total);
 }
 
-
-
+// iota, then keys -> keys_out with the positions -> perm.
+gcg_status sort_with_positions(const SortSpace& s, int64_t n, int end_bit, const int32_t* keys,
+                               int32_t* perm, hipStream_t st) {
+  hipLaunchKernelGGL(iota_kernel, dim3(grid_for(n)), dim3(256), 0, st, s.iota, n);
+  GCG_HIP_CHECK(hipGetLastError());
+  GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceRadixSort::SortPairs, reinterpret_cast<const uint32_t*>(keys),
+      reinterpret_cast<uint32_t*>(s.keys_out), s.iota, perm, static_cast<int>(n), 0, end_bit, st)));
+  return GCG_OK;
+}
 
 // Rectify backward + bias gradient in one pass (Theano's grad of
 // rectify(S.dot(H, Z) + b), mlpconv.py:75-77): g = gY where Y > 0 else 0, written to g_out
@@ -347,29 +362,21 @@ gcg_status gcg_index_csr(int64_t n_idx, const int32_t* idx, int64_t n_rows, int3
                          size_t* workspace_needed, gcg_stream_t stream) {
   if (n_idx < 0 || n_idx > INT32_MAX || n_rows < 0 || n_rows >= INT32_MAX)
     return fail(GCG_ERR_INVALID_ARG, "bad sizes");
-  const int end_bit = bits_for(n_rows + 1);
-  size_t temp = 0;
-  if (gcg_status s = sort_pairs_ws(n_idx, end_bit, &temp)) return s;
-  const size_t nb = align_up(static_cast<size_t>(n_idx) * sizeof(int32_t), 256);
-  const size_t need = 2 * nb + align_up(temp, 256);
-  if (workspace_needed) *workspace_needed = need;
+  const int end_bit = bits_to_count(n_rows + 1);
+  SortSpace s;
+  if (gcg_status rc = sort_space("gcg_index_csr", n_idx, end_bit, 0, workspace, &s)) return rc;
+  if (workspace_needed) *workspace_needed = s.total;
   if (seg_ptr == nullptr && sorted_pos == nullptr) return GCG_OK;  // sizing query
   if (seg_ptr == nullptr || (n_idx > 0 && (idx == nullptr || sorted_pos == nullptr)))
     return fail(GCG_ERR_INVALID_ARG, "NULL buffer");
-  if (workspace_bytes < need || (need > 0 && workspace == nullptr))
-    return fail(GCG_ERR_WORKSPACE, "workspace %zu < %zu", workspace_bytes, need);
+  // (this entry and the transpose have never asked the workspace for an alignment: 1)
+  if (s.total > 0)  // nothing to sort and no temporary: no workspace
+    if (gcg_status rc = check_workspace("gcg_index_csr", workspace, workspace_bytes, s.total, 1))
+      return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(workspace);
-  int32_t* keys_out = reinterpret_cast<int32_t*>(w);
-  int32_t* vals_in = reinterpret_cast<int32_t*>(w + nb);
-  void* cub_tmp = w + 2 * nb;
-  if (n_idx > 0) {
-    hipLaunchKernelGGL(iota_kernel, dim3(grid_for(n_idx)), dim3(256), 0, st, vals_in, n_idx);
-    GCG_HIP_CHECK(hipGetLastError());
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(cub_tmp, temp, reinterpret_cast<const uint32_t*>(idx), reinterpret_cast<uint32_t*>(keys_out), vals_in, sorted_pos,
-                                                     static_cast<int>(n_idx), 0, end_bit, st));
-  }
-  hipLaunchKernelGGL(lower_bound_kernel, dim3(grid_for(n_rows + 1)), dim3(256), 0, st, keys_out,
+  if (n_idx > 0)
+    if (gcg_status rc = sort_with_positions(s, n_idx, end_bit, idx, sorted_pos, st)) return rc;
+  hipLaunchKernelGGL(lower_bound_kernel, dim3(grid_for(n_rows + 1)), dim3(256), 0, st, s.keys_out,
                      n_idx, n_rows, seg_ptr);
   GCG_HIP_CHECK(hipGetLastError());
   return GCG_OK;
@@ -396,43 +403,32 @@ gcg_status gcg_csr_transpose_f32(int64_t n_rows, int64_t n_cols, int64_t nnz,
                                  size_t* workspace_needed, gcg_stream_t stream) {
   if (n_rows < 0 || n_cols < 0 || nnz < 0 || nnz > INT32_MAX || n_cols >= INT32_MAX)
     return fail(GCG_ERR_INVALID_ARG, "bad sizes");
-  const int end_bit = bits_for(n_cols + 1);
-  size_t temp = 0;
-  if (gcg_status s = sort_pairs_ws(nnz, end_bit, &temp)) return s;
-  const size_t nb = align_up(static_cast<size_t>(nnz) * sizeof(int32_t), 256);
-  // [sorted cols][iota][perm][row_of][cub temp]
-  const size_t need = 4 * nb + align_up(temp, 256);
-  if (workspace_needed) *workspace_needed = need;
+  const int end_bit = bits_to_count(n_cols + 1);
+  SortSpace s;  // sorted columns, iota, then perm and row_of
+  if (gcg_status rc = sort_space("gcg_csr_transpose_f32", nnz, end_bit, 2, workspace, &s)) return rc;
+  if (workspace_needed) *workspace_needed = s.total;
   if (out_indptr == nullptr && out_indices == nullptr && out_vals == nullptr) return GCG_OK;
   if (out_indptr == nullptr || indptr == nullptr ||
       (nnz > 0 && (indices == nullptr || vals == nullptr || out_indices == nullptr || out_vals == nullptr)))
     return fail(GCG_ERR_INVALID_ARG, "NULL buffer");
-  if (workspace_bytes < need || (need > 0 && workspace == nullptr))
-    return fail(GCG_ERR_WORKSPACE, "workspace %zu < %zu", workspace_bytes, need);
+  if (s.total > 0)  // no entry and no temporary: no workspace
+    if (gcg_status rc = check_workspace("gcg_csr_transpose_f32", workspace, workspace_bytes, s.total, 1))
+      return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(workspace);
-  int32_t* keys_out = reinterpret_cast<int32_t*>(w);
-  int32_t* iota = reinterpret_cast<int32_t*>(w + nb);
-  int32_t* perm = reinterpret_cast<int32_t*>(w + 2 * nb);
-  int32_t* row_of = reinterpret_cast<int32_t*>(w + 3 * nb);
-  void* cub_tmp = w + 4 * nb;
+  int32_t *perm = s.extra[0], *row_of = s.extra[1];
   if (nnz > 0) {
-    hipLaunchKernelGGL(iota_kernel, dim3(grid_for(nnz)), dim3(256), 0, st, iota, nnz);
-    GCG_HIP_CHECK(hipGetLastError());
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(cub_tmp, temp, reinterpret_cast<const uint32_t*>(indices), reinterpret_cast<uint32_t*>(keys_out), iota, perm,
-                                                     static_cast<int>(nnz), 0, end_bit, st));
+    if (gcg_status rc = sort_with_positions(s, nnz, end_bit, indices, perm, st)) return rc;
     hipLaunchKernelGGL(expand_rows_kernel, dim3(grid_for(n_rows)), dim3(256), 0, st, n_rows, indptr, row_of);
     GCG_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(permute_transpose_kernel, dim3(grid_for(nnz)), dim3(256), 0, st, nnz, perm,
                        row_of, vals, out_indices, out_vals);
     GCG_HIP_CHECK(hipGetLastError());
   }
-  hipLaunchKernelGGL(lower_bound_kernel, dim3(grid_for(n_cols + 1)), dim3(256), 0, st, keys_out,
+  hipLaunchKernelGGL(lower_bound_kernel, dim3(grid_for(n_cols + 1)), dim3(256), 0, st, s.keys_out,
                      nnz, n_cols, out_indptr);
   GCG_HIP_CHECK(hipGetLastError());
   return GCG_OK;
 }
-
 
 gcg_status gcg_relu_backward_f32_workspace_bytes(int64_t M, int64_t K, size_t* bytes) {
   if (M < 0 || K < 0 || bytes == nullptr)

@@ -13,7 +13,7 @@
 
 #include <cmath>
 
-#include "common.h"
+#include "scratch.h"
 #include "segment_kernels.h"
 
 using namespace gcg;
@@ -24,17 +24,6 @@ constexpr double kDegToRad = 3.14159265358979323846 / 180.0;
 // medians staged per LDS tile of nearest_class_kernel: 3 doubles each, 48 KiB, so two
 // workgroups still share a CU's LDS
 constexpr int kClassTile = 2048;
-
-struct DevMem {
-  void* p = nullptr;
-  hipStream_t s = nullptr;
-  ~DevMem() { if (p) (void)hipFreeAsync(p, s); }
-  hipError_t alloc(size_t bytes, hipStream_t st) {
-    s = st;
-    return hipMallocAsync(&p, std::max<size_t>(bytes, 16), st);
-  }
-  template <typename T> T* as() const { return static_cast<T*>(p); }
-};
 
 // locs (N x 2 row-major) -> vals[0..N) latitudes, vals[N..2N) longitudes; ids = 0..N-1;
 // a non-finite coordinate raises *status.
@@ -351,58 +340,55 @@ gcg_status gcg_kdtree_fit_f64(int64_t N, const double* locs, int64_t bucket_size
       !aligned(leaf_ptr, 4) || !aligned(status_dev, 4))
     return fail(GCG_ERR_MISALIGNED, "gcg_kdtree_fit_f64: operand not aligned to its element");
   const int n = static_cast<int>(N), n_scan = 2 * n + 2;
-  size_t t_sort = 0, t_ex = 0, t_inc = 0;
-  {
-    double* k = nullptr;
-    int32_t* v = nullptr;
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, t_sort, k, k, v, v, n));
-    GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t_ex, v, v, n_scan));
-    GCG_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, t_inc, v, v, n));
-  }
-  const size_t tb = std::max({t_sort, t_ex, t_inc});
   const size_t ib = static_cast<size_t>(N) * sizeof(int32_t);
-  DevMem vals, keys, iota, ids[2][2], head[2], end[2], done, dim, split, flags, ex, tmp, small;
-  GCG_HIP_CHECK(vals.alloc(2 * static_cast<size_t>(N) * sizeof(double), st));
-  GCG_HIP_CHECK(keys.alloc(static_cast<size_t>(N) * sizeof(double), st));
-  GCG_HIP_CHECK(iota.alloc(ib, st));
-  for (auto& pair : ids)
-    for (auto& m : pair) GCG_HIP_CHECK(m.alloc(ib, st));
-  for (auto& m : head) GCG_HIP_CHECK(m.alloc(ib, st));
-  for (auto& m : end) GCG_HIP_CHECK(m.alloc(ib, st));
-  GCG_HIP_CHECK(done.alloc(ib, st));
-  GCG_HIP_CHECK(dim.alloc(ib, st));
-  GCG_HIP_CHECK(split.alloc(static_cast<size_t>(N) * sizeof(double), st));
-  GCG_HIP_CHECK(flags.alloc(static_cast<size_t>(n_scan) * sizeof(int32_t), st));
-  GCG_HIP_CHECK(ex.alloc(static_cast<size_t>(n_scan) * sizeof(int32_t), st));
-  GCG_HIP_CHECK(tmp.alloc(tb, st));
-  GCG_HIP_CHECK(small.alloc(16, st));  // int32 any_split | pad | int64 n_leaves
-  int32_t* any_split = small.as<int32_t>();
-  int64_t* n_leaves = reinterpret_cast<int64_t*>(small.as<char>() + 8);
+  double *vals = nullptr, *keys = nullptr, *split = nullptr;
+  int32_t *iota = nullptr, *ids[2][2] = {}, *head[2] = {}, *end[2] = {}, *done = nullptr,
+          *dim = nullptr, *flags = nullptr, *ex = nullptr, *any_split = nullptr;
+  int64_t* n_leaves = nullptr;
+  Tmp tmp;
+  TmpSize ts;
+  ts.add(GCG_CUB(DeviceRadixSort::SortPairs, vals, keys, iota, ids[0][0], n));
+  ts.add(GCG_CUB(DeviceScan::ExclusiveSum, flags, ex, n_scan));
+  ts.add(GCG_CUB(DeviceScan::InclusiveSum, flags, ex, n));
+  if (gcg_status rc = ts.status("gcg_kdtree_fit_f64")) return rc;
+  DevMem mem;
+  GCG_HIP_CHECK(alloc_carved(mem, st, [&](Carver& cv) {
+    vals = cv.take<double>(2 * N);
+    keys = cv.take<double>(N);
+    iota = cv.take<int32_t>(N);
+    for (auto& pair : ids)
+      for (auto& m : pair) m = cv.take<int32_t>(N);
+    for (auto& m : head) m = cv.take<int32_t>(N);
+    for (auto& m : end) m = cv.take<int32_t>(N);
+    done = cv.take<int32_t>(N);
+    dim = cv.take<int32_t>(N);
+    split = cv.take<double>(N);
+    flags = cv.take<int32_t>(n_scan);
+    ex = cv.take<int32_t>(n_scan);
+    any_split = cv.take<int32_t>(1);
+    n_leaves = cv.take<int64_t>(1);
+    tmp = {cv.take<char>(ts.bytes), ts.bytes};
+  }));
   const dim3 g1(grid_for(N)), g2(grid_for(2 * N)), blk(256);
 
   GCG_HIP_CHECK(hipMemsetAsync(status_dev, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(split_coords_kernel, g1, blk, 0, st, N, locs, vals.as<double>(),
-                     iota.as<int32_t>(), status_dev);
+  hipLaunchKernelGGL(split_coords_kernel, g1, blk, 0, st, N, locs, vals, iota, status_dev);
   GCG_HIP_CHECK(hipGetLastError());
   // presort: ids[d][0] = the point ids by coordinate d
   for (int d = 0; d < 2; ++d) {
-    size_t t = tb;
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
-        tmp.p, t, vals.as<double>() + d * N, keys.as<double>(), iota.as<int32_t>(),
-        ids[d][0].as<int32_t>(), n, 0, 64, st));
+    GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceRadixSort::SortPairs, vals + d * N, keys, iota, ids[d][0], n, 0, 64,
+        st)));
   }
-  hipLaunchKernelGGL(tree_init_kernel, g1, blk, 0, st, N, head[0].as<int32_t>(),
-                     end[0].as<int32_t>(), done.as<int32_t>());
+  hipLaunchKernelGGL(tree_init_kernel, g1, blk, 0, st, N, head[0], end[0], done);
   GCG_HIP_CHECK(hipGetLastError());
 
   int cur = 0;
   int64_t depth = 0, readbacks = 0;
   for (;;) {
     GCG_HIP_CHECK(hipMemsetAsync(any_split, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(tree_node_kernel, g1, blk, 0, st, N, bucket_size, vals.as<double>(),
-                       ids[0][cur].as<int32_t>(), ids[1][cur].as<int32_t>(),
-                       head[cur].as<int32_t>(), end[cur].as<int32_t>(), done.as<int32_t>(),
-                       dim.as<int32_t>(), split.as<double>(), any_split, status_dev);
+    hipLaunchKernelGGL(tree_node_kernel, g1, blk, 0, st, N, bucket_size, vals,
+                       ids[0][cur], ids[1][cur], head[cur], end[cur], done, dim, split, any_split,
+                       status_dev);
     GCG_HIP_CHECK(hipGetLastError());
     // the level's one scalar readback: did any node split (2: the input check failed)
     int32_t host = 0;
@@ -416,33 +402,25 @@ gcg_status gcg_kdtree_fit_f64(int64_t N, const double* locs, int64_t bucket_size
     if (host == 0) break;
     if (++depth > N) return fail(GCG_ERR_HIP, "gcg_kdtree_fit_f64: tree deeper than N");
     const int nxt = cur ^ 1;
-    hipLaunchKernelGGL(tree_flag_kernel, g2, blk, 0, st, N, vals.as<double>(),
-                       ids[0][cur].as<int32_t>(), ids[1][cur].as<int32_t>(),
-                       head[cur].as<int32_t>(), dim.as<int32_t>(), split.as<double>(),
-                       flags.as<int32_t>());
+    hipLaunchKernelGGL(tree_flag_kernel, g2, blk, 0, st, N, vals, ids[0][cur],
+                       ids[1][cur], head[cur], dim, split, flags);
     GCG_HIP_CHECK(hipGetLastError());
-    size_t t = tb;
-    GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, t, flags.as<int32_t>(), ex.as<int32_t>(),
-                                                   n_scan, st));
-    hipLaunchKernelGGL(tree_scatter_kernel, g2, blk, 0, st, N, flags.as<int32_t>(),
-                       ex.as<int32_t>(), ids[0][cur].as<int32_t>(), ids[1][cur].as<int32_t>(),
-                       head[cur].as<int32_t>(), end[cur].as<int32_t>(), dim.as<int32_t>(),
-                       ids[0][nxt].as<int32_t>(), ids[1][nxt].as<int32_t>(),
-                       head[nxt].as<int32_t>(), end[nxt].as<int32_t>(), done.as<int32_t>());
+    GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceScan::ExclusiveSum, flags, ex, n_scan, st)));
+    hipLaunchKernelGGL(tree_scatter_kernel, g2, blk, 0, st, N, flags, ex, ids[0][cur],
+                       ids[1][cur], head[cur], end[cur], dim, ids[0][nxt], ids[1][nxt], head[nxt],
+                       end[nxt], done);
     GCG_HIP_CHECK(hipGetLastError());
     cur = nxt;
   }
   // leaves in segment order = the reference's pre-order numbering
-  hipLaunchKernelGGL(tree_head_flag_kernel, g1, blk, 0, st, N, head[cur].as<int32_t>(),
-                     flags.as<int32_t>());
+  hipLaunchKernelGGL(tree_head_flag_kernel, g1, blk, 0, st, N, head[cur], flags);
   GCG_HIP_CHECK(hipGetLastError());
-  size_t t = tb;
-  GCG_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(tmp.p, t, flags.as<int32_t>(), ex.as<int32_t>(), n, st));
-  hipLaunchKernelGGL(tree_label_kernel, g1, blk, 0, st, N, ex.as<int32_t>(),
-                     head[cur].as<int32_t>(), ids[0][cur].as<int32_t>(), labels, leaf_ptr, n_leaves);
+  GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceScan::InclusiveSum, flags, ex, n, st)));
+  hipLaunchKernelGGL(tree_label_kernel, g1, blk, 0, st, N, ex, head[cur],
+                     ids[0][cur], labels, leaf_ptr, n_leaves);
   GCG_HIP_CHECK(hipGetLastError());
-  GCG_HIP_CHECK(hipMemcpyAsync(perm_lat, ids[0][cur].p, ib, hipMemcpyDeviceToDevice, st));
-  GCG_HIP_CHECK(hipMemcpyAsync(perm_lon, ids[1][cur].p, ib, hipMemcpyDeviceToDevice, st));
+  GCG_HIP_CHECK(hipMemcpyAsync(perm_lat, ids[0][cur], ib, hipMemcpyDeviceToDevice, st));
+  GCG_HIP_CHECK(hipMemcpyAsync(perm_lon, ids[1][cur], ib, hipMemcpyDeviceToDevice, st));
   int64_t nl = 0;
   GCG_HIP_CHECK(hipMemcpyAsync(&nl, n_leaves, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   GCG_HIP_CHECK(hipStreamSynchronize(st));
@@ -488,53 +466,50 @@ gcg_status gcg_class_medians_f64(int64_t N, const double* locs, const int32_t* l
   if (!aligned(locs, 8) || !aligned(medians, 8) || !aligned(labels, 4) || !aligned(status_dev, 4))
     return fail(GCG_ERR_MISALIGNED, "gcg_class_medians_f64: operand not aligned to its element");
   const int n = static_cast<int>(N);
-  const int lbits = bits_for(C);
-  size_t t1 = 0, t2 = 0;
+  const int lbits = bits_to_count(C);
+  double *vals = nullptr, *keys = nullptr;
+  int32_t *iota = nullptr, *by_val = nullptr, *lab = nullptr, *lab_sorted = nullptr,
+          *perm[2] = {}, *ptr = nullptr;
+  Tmp tmp;
+  TmpSize ts;
   if (N > 0) {
-    double* k = nullptr;
-    int32_t* v = nullptr;
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, k, k, v, v, n));
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, t2, v, v, v, v, n, 0, lbits));
+    ts.add(GCG_CUB(DeviceRadixSort::SortPairs, vals, keys, iota, by_val, n));
+    ts.add(GCG_CUB(DeviceRadixSort::SortPairs, lab, lab_sorted, by_val, perm[0], n, 0, lbits));
+    if (gcg_status rc = ts.status("gcg_class_medians_f64")) return rc;
   }
-  const size_t tb = std::max(t1, t2);
-  const size_t ib = static_cast<size_t>(N) * sizeof(int32_t);
-  DevMem vals, keys, iota, by_val, lab, lab_sorted, perm[2], ptr, tmp;
-  GCG_HIP_CHECK(vals.alloc(2 * static_cast<size_t>(N) * sizeof(double), st));
-  GCG_HIP_CHECK(keys.alloc(static_cast<size_t>(N) * sizeof(double), st));
-  GCG_HIP_CHECK(iota.alloc(ib, st));
-  GCG_HIP_CHECK(by_val.alloc(ib, st));
-  GCG_HIP_CHECK(lab.alloc(ib, st));
-  GCG_HIP_CHECK(lab_sorted.alloc(ib, st));
-  for (auto& m : perm) GCG_HIP_CHECK(m.alloc(ib, st));
-  GCG_HIP_CHECK(ptr.alloc(static_cast<size_t>(C + 1) * sizeof(int32_t), st));
-  GCG_HIP_CHECK(tmp.alloc(tb, st));
+  DevMem mem;
+  GCG_HIP_CHECK(alloc_carved(mem, st, [&](Carver& cv) {
+    vals = cv.take<double>(2 * N);
+    keys = cv.take<double>(N);
+    iota = cv.take<int32_t>(N);
+    by_val = cv.take<int32_t>(N);
+    lab = cv.take<int32_t>(N);
+    lab_sorted = cv.take<int32_t>(N);
+    for (auto& m : perm) m = cv.take<int32_t>(N);
+    ptr = cv.take<int32_t>(C + 1);
+    tmp = {cv.take<char>(ts.bytes), ts.bytes};
+  }));
   const dim3 g1(grid_for(N)), blk(256);
   if (N > 0) {
-    hipLaunchKernelGGL(split_coords_kernel, g1, blk, 0, st, N, locs, vals.as<double>(),
-                       iota.as<int32_t>(), status_dev);
+    hipLaunchKernelGGL(split_coords_kernel, g1, blk, 0, st, N, locs, vals, iota,
+                       status_dev);
     GCG_HIP_CHECK(hipGetLastError());
     // by value, then (stably) by class: each class's run is sorted by the coordinate
     for (int d = 0; d < 2; ++d) {
-      size_t t = tb;
-      GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
-          tmp.p, t, vals.as<double>() + d * N, keys.as<double>(), iota.as<int32_t>(),
-          by_val.as<int32_t>(), n, 0, 64, st));
-      hipLaunchKernelGGL(gather_labels_kernel, g1, blk, 0, st, N, C, labels, by_val.as<int32_t>(),
-                         lab.as<int32_t>(), status_dev);
+      GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceRadixSort::SortPairs, vals + d * N, keys, iota, by_val, n, 0, 64,
+          st)));
+      hipLaunchKernelGGL(gather_labels_kernel, g1, blk, 0, st, N, C, labels, by_val, lab,
+                         status_dev);
       GCG_HIP_CHECK(hipGetLastError());
-      t = tb;
-      GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
-          tmp.p, t, lab.as<int32_t>(), lab_sorted.as<int32_t>(), by_val.as<int32_t>(),
-          perm[d].as<int32_t>(), n, 0, lbits, st));
+      GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceRadixSort::SortPairs, lab, lab_sorted, by_val, perm[d], n, 0, lbits,
+          st)));
     }
   }
-  hipLaunchKernelGGL(class_ptr_kernel, dim3(grid_for(N + 1)), blk, 0, st, N, C,
-                     lab_sorted.as<int32_t>(), ptr.as<int32_t>());
+  hipLaunchKernelGGL(class_ptr_kernel, dim3(grid_for(N + 1)), blk, 0, st, N, C, lab_sorted,
+                     ptr);
   GCG_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(segment_medians_kernel, dim3(grid_for(C)), blk, 0, st, C, N,
-                     vals.as<double>(), vals.as<double>() + N, int64_t{1}, ptr.as<int32_t>(),
-                     perm[0].as<int32_t>(),
-                     perm[1].as<int32_t>(), medians);
+                     vals, vals + N, int64_t{1}, ptr, perm[0], perm[1], medians);
   GCG_HIP_CHECK(hipGetLastError());
   return GCG_OK;
 }

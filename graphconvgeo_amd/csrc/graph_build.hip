@@ -7,7 +7,7 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "scratch.h"
 
 using namespace gcg;
 
@@ -205,18 +205,26 @@ __global__ void decode_pairs_kernel(int64_t n_targets, const uint64_t* __restric
   }
 }
 
-struct DevMem {
-  void* p = nullptr;
-  hipStream_t s = nullptr;
-  ~DevMem() { if (p) (void)hipFreeAsync(p, s); }
-  hipError_t alloc(size_t bytes, hipStream_t st) { s = st; return hipMallocAsync(&p, std::max<size_t>(bytes, 16), st); }
-  template <typename T> T* as() const { return static_cast<T*>(p); }
+// The scratch of the normalisation: the m edge keys, their sorted copy (then the unique keys go
+// back to `keys`), the n inverse root degrees, hipcub's temporary. take_exact: no edge or no
+// node, empty arrays.
+struct NormSpace {
+  uint64_t *keys, *sorted;
+  double* dinv;
+  Tmp tmp;
+  size_t total;
 };
 
-int key_bits(uint64_t max_key) {
-  int b = 1;
-  while (b < 64 && (uint64_t{1} << b) <= max_key) ++b;
-  return b;
+gcg_status norm_space(const char* fn, int64_t n, int64_t m, int end_bit, int64_t* nnz_dev,
+                      void* workspace, NormSpace* s) {
+  Carver cv(workspace);
+  s->keys = cv.take_exact<uint64_t>(m);
+  s->sorted = cv.take_exact<uint64_t>(m);
+  s->dinv = cv.take_exact<double>(n);
+  TmpSize ts;
+  ts.add(GCG_CUB(DeviceRadixSort::SortKeys, s->keys, s->sorted, static_cast<int>(m), 0, end_bit));
+  ts.add(GCG_CUB(DeviceSelect::Unique, s->sorted, s->keys, nnz_dev, static_cast<int>(m)));
+  return ts.take_exact(fn, cv, &s->tmp, &s->total);
 }
 }  // namespace
 
@@ -232,43 +240,30 @@ gcg_status gcg_normalize_adjacency_f32(int64_t n, int64_t n_edges, const int32_t
     return fail(GCG_ERR_INVALID_ARG, "bad sizes");
   const int64_t m = 2 * n_edges + (self_loops ? n : 0);
   if (m > INT32_MAX) return fail(GCG_ERR_INVALID_ARG, "too many entries for int32 CSR");
-  int end_bit = 1;
-  while (end_bit < 64 && (uint64_t{1} << end_bit) <= static_cast<uint64_t>(n) * n) ++end_bit;
-  size_t t_sort = 0, t_uniq = 0;
-  {
-    uint64_t* k = nullptr;
-    int64_t* cnt = nullptr;
-    if (hipcub::DeviceRadixSort::SortKeys(nullptr, t_sort, k, k, static_cast<int>(m), 0, end_bit) != hipSuccess ||
-        hipcub::DeviceSelect::Unique(nullptr, t_uniq, k, k, cnt, static_cast<int>(m)) != hipSuccess)
-      return fail(GCG_ERR_HIP, "hipcub sizing failed");
-  }
-  const size_t kb = align_up(static_cast<size_t>(m) * sizeof(uint64_t), 256);
-  const size_t db = align_up(static_cast<size_t>(n) * sizeof(double), 256);
-  const size_t need = 2 * kb + db + align_up(std::max(t_sort, t_uniq), 256);
-  if (workspace_needed) *workspace_needed = need;
+  const char* fn = "gcg_normalize_adjacency_f32";
+  const int end_bit = bits_to_hold(static_cast<uint64_t>(n) * n);
+  NormSpace s;
+  if (gcg_status rc = norm_space(fn, n, m, end_bit, nnz_dev, workspace, &s)) return rc;
+  if (workspace_needed) *workspace_needed = s.total;
   if (indptr == nullptr && indices == nullptr && vals == nullptr) return GCG_OK;  // sizing
   if (indptr == nullptr || nnz_dev == nullptr || status_dev == nullptr ||
       (m > 0 && (indices == nullptr || vals == nullptr)) || (n_edges > 0 && (u == nullptr || v == nullptr)))
     return fail(GCG_ERR_INVALID_ARG, "NULL buffer");
-  if (workspace_bytes < need || workspace == nullptr)
-    return fail(GCG_ERR_WORKSPACE, "workspace %zu < %zu", workspace_bytes, need);
+  // (the entry has never asked the workspace for an alignment: 1)
+  if (gcg_status rc = check_workspace(fn, workspace, workspace_bytes, s.total, 1)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(workspace);
-  uint64_t* keys = reinterpret_cast<uint64_t*>(w);
-  uint64_t* sorted = reinterpret_cast<uint64_t*>(w + kb);
-  double* dinv = reinterpret_cast<double*>(w + 2 * kb);
-  void* tmp = w + 2 * kb + db;
+  uint64_t *keys = s.keys, *sorted = s.sorted;
+  double* dinv = s.dinv;
   GCG_HIP_CHECK(hipMemsetAsync(status_dev, 0, sizeof(int32_t), st));
   GCG_HIP_CHECK(hipMemsetAsync(nnz_dev, 0, sizeof(int64_t), st));
   if (m > 0) {
     hipLaunchKernelGGL(edge_keys_kernel, dim3(grid_for(std::max(n_edges, n))), dim3(256), 0, st, n,
                        n_edges, u, v, self_loops, keys, status_dev);
     GCG_HIP_CHECK(hipGetLastError());
-    size_t ts = t_sort;
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(tmp, ts, keys, sorted, static_cast<int>(m), 0, end_bit, st));
-    size_t tu = t_uniq;
+    GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceRadixSort::SortKeys, keys, sorted, static_cast<int>(m), 0, end_bit,
+        st)));
     // Duplicate edges collapse (binary adjacency, as networkx holds one edge per pair).
-    GCG_HIP_CHECK(hipcub::DeviceSelect::Unique(tmp, tu, sorted, keys, nnz_dev, static_cast<int>(m), st));
+    GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceSelect::Unique, sorted, keys, nnz_dev, static_cast<int>(m), st)));
     hipLaunchKernelGGL(keys_to_csr_kernel, dim3(grid_for(m)), dim3(256), 0, st, n, keys, nnz_dev, indices);
     GCG_HIP_CHECK(hipGetLastError());
   }
@@ -281,8 +276,6 @@ gcg_status gcg_normalize_adjacency_f32(int64_t n, int64_t n_edges, const int32_t
   GCG_HIP_CHECK(hipGetLastError());
   return GCG_OK;
 }
-
-
 
 gcg_status gcg_project_mention_graph(int64_t n_targets, int64_t n_nodes, int64_t n_inc,
                                      const int32_t* a, const int32_t* b, int celebrity_threshold,
@@ -299,56 +292,53 @@ gcg_status gcg_project_mention_graph(int64_t n_targets, int64_t n_nodes, int64_t
   if (n_targets < 2) return GCG_OK;
   const int64_t m2 = 2 * n_inc;
   const uint64_t M = static_cast<uint64_t>(n_nodes);
-  DevMem keys, keys2, cnt, ptr, tcount, npairs, toff, poff, tmp;
-  size_t tb = 0;
+  const char* fn = "gcg_project_mention_graph";
+  const int adj_bits = bits_to_hold(M * M);
   // 1. symmetric, deduplicated adjacency of g
-  {
-    uint64_t* k = nullptr; int64_t* c = nullptr; int64_t* o = nullptr;
-    size_t t1 = 0, t2 = 0, t3 = 0;
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, k, k, static_cast<int>(std::max<int64_t>(m2, 1)), 0, key_bits(M * M)));
-    GCG_HIP_CHECK(hipcub::DeviceSelect::Unique(nullptr, t2, k, k, c, static_cast<int>(std::max<int64_t>(m2, 1))));
-    GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, o, o, static_cast<int>(n_nodes)));
-    tb = std::max({t1, t2, t3});
-  }
-  GCG_HIP_CHECK(keys.alloc(m2 * sizeof(uint64_t), st));
-  GCG_HIP_CHECK(keys2.alloc(m2 * sizeof(uint64_t), st));
-  GCG_HIP_CHECK(cnt.alloc(2 * sizeof(int64_t), st));
-  GCG_HIP_CHECK(ptr.alloc((n_nodes + 1) * sizeof(int64_t), st));
-  GCG_HIP_CHECK(tcount.alloc(n_nodes * sizeof(int64_t), st));
-  GCG_HIP_CHECK(npairs.alloc(n_nodes * sizeof(int64_t), st));
-  GCG_HIP_CHECK(toff.alloc(n_nodes * sizeof(int64_t), st));
-  GCG_HIP_CHECK(poff.alloc(n_nodes * sizeof(int64_t), st));
-  GCG_HIP_CHECK(tmp.alloc(tb, st));
-  GCG_HIP_CHECK(hipMemsetAsync(cnt.p, 0, 2 * sizeof(int64_t), st));
+  uint64_t *keys = nullptr, *keys2 = nullptr;
+  int64_t *cnt = nullptr, *ptr = nullptr, *tcount = nullptr, *npairs = nullptr, *toff = nullptr,
+          *poff = nullptr;
+  Tmp tmp;
+  const int n = static_cast<int>(std::max<int64_t>(m2, 1));
+  TmpSize ts;
+  ts.add(GCG_CUB(DeviceRadixSort::SortKeys, keys, keys2, n, 0, adj_bits));
+  ts.add(GCG_CUB(DeviceSelect::Unique, keys2, keys, cnt, n));
+  ts.add(GCG_CUB(DeviceScan::ExclusiveSum, tcount, toff, static_cast<int>(n_nodes)));
+  if (gcg_status rc = ts.status(fn)) return rc;
+  DevMem mem;
+  GCG_HIP_CHECK(alloc_carved(mem, st, [&](Carver& cv) {
+    keys = cv.take<uint64_t>(m2);
+    keys2 = cv.take<uint64_t>(m2);
+    cnt = cv.take<int64_t>(2);
+    ptr = cv.take<int64_t>(n_nodes + 1);
+    tcount = cv.take<int64_t>(n_nodes);
+    npairs = cv.take<int64_t>(n_nodes);
+    toff = cv.take<int64_t>(n_nodes);
+    poff = cv.take<int64_t>(n_nodes);
+    tmp = {cv.take<char>(ts.bytes), ts.bytes};
+  }));
+  GCG_HIP_CHECK(hipMemsetAsync(cnt, 0, 2 * sizeof(int64_t), st));
   if (m2 > 0) {
     hipLaunchKernelGGL(incidence_keys_kernel, dim3(grid_for(n_inc)), dim3(256), 0, st, n_nodes, n_inc, a, b,
-                       keys.as<uint64_t>(), status_dev);
+                       keys, status_dev);
     GCG_HIP_CHECK(hipGetLastError());
-    size_t t = tb;
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(tmp.p, t, keys.as<uint64_t>(), keys2.as<uint64_t>(),
-                                                    static_cast<int>(m2), 0, key_bits(M * M), st));
-    t = tb;
-    GCG_HIP_CHECK(hipcub::DeviceSelect::Unique(tmp.p, t, keys2.as<uint64_t>(), keys.as<uint64_t>(),
-                                               cnt.as<int64_t>(), static_cast<int>(m2), st));
+    GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceRadixSort::SortKeys, keys, keys2, static_cast<int>(m2), 0, adj_bits,
+        st)));
+    GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceSelect::Unique, keys2, keys, cnt, static_cast<int>(m2), st)));
   }
-  hipLaunchKernelGGL(adj_ptr_kernel, dim3(grid_for(n_nodes + 1)), dim3(256), 0, st, n_nodes,
-                     keys.as<uint64_t>(), cnt.as<int64_t>(), ptr.as<int64_t>());
+  hipLaunchKernelGGL(adj_ptr_kernel, dim3(grid_for(n_nodes + 1)), dim3(256), 0, st, n_nodes, keys, cnt,
+                     ptr);
   // 2-3. celebrity filter, user-neighbour lists, pair counts
   hipLaunchKernelGGL(target_count_kernel, dim3(grid_for(n_nodes)), dim3(256), 0, st, n_targets, n_nodes,
-                     celebrity_threshold, ptr.as<int64_t>(), keys.as<uint64_t>(), tcount.as<int64_t>(),
-                     npairs.as<int64_t>());
+                     celebrity_threshold, ptr, keys, tcount, npairs);
   GCG_HIP_CHECK(hipGetLastError());
-  size_t t = tb;
-  GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, t, tcount.as<int64_t>(), toff.as<int64_t>(),
-                                                 static_cast<int>(n_nodes), st));
-  t = tb;
-  GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, t, npairs.as<int64_t>(), poff.as<int64_t>(),
-                                                 static_cast<int>(n_nodes), st));
+  GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceScan::ExclusiveSum, tcount, toff, static_cast<int>(n_nodes), st)));
+  GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceScan::ExclusiveSum, npairs, poff, static_cast<int>(n_nodes), st)));
   int64_t last[4] = {0, 0, 0, 0};  // toff[M-1], tcount[M-1], poff[M-1], npairs[M-1]
-  GCG_HIP_CHECK(hipMemcpyAsync(&last[0], toff.as<int64_t>() + n_nodes - 1, 8, hipMemcpyDeviceToHost, st));
-  GCG_HIP_CHECK(hipMemcpyAsync(&last[1], tcount.as<int64_t>() + n_nodes - 1, 8, hipMemcpyDeviceToHost, st));
-  GCG_HIP_CHECK(hipMemcpyAsync(&last[2], poff.as<int64_t>() + n_nodes - 1, 8, hipMemcpyDeviceToHost, st));
-  GCG_HIP_CHECK(hipMemcpyAsync(&last[3], npairs.as<int64_t>() + n_nodes - 1, 8, hipMemcpyDeviceToHost, st));
+  GCG_HIP_CHECK(hipMemcpyAsync(&last[0], toff + n_nodes - 1, 8, hipMemcpyDeviceToHost, st));
+  GCG_HIP_CHECK(hipMemcpyAsync(&last[1], tcount + n_nodes - 1, 8, hipMemcpyDeviceToHost, st));
+  GCG_HIP_CHECK(hipMemcpyAsync(&last[2], poff + n_nodes - 1, 8, hipMemcpyDeviceToHost, st));
+  GCG_HIP_CHECK(hipMemcpyAsync(&last[3], npairs + n_nodes - 1, 8, hipMemcpyDeviceToHost, st));
   GCG_HIP_CHECK(hipStreamSynchronize(st));
   const int64_t n_tlist = last[0] + last[1], P = last[2] + last[3];
   if (sizing) {  // capacity query: the number of pairs bounds the number of edges
@@ -357,46 +347,44 @@ gcg_status gcg_project_mention_graph(int64_t n_targets, int64_t n_nodes, int64_t
   }
   if (P == 0) return GCG_OK;
   if (P > INT32_MAX) return fail(GCG_ERR_INVALID_ARG, "%lld projected pairs exceed the int32 sort range", (long long)P);
-  DevMem tlist, pk, pk2, ucnt, tmp2;
-  GCG_HIP_CHECK(tlist.alloc(n_tlist * sizeof(int32_t), st));
-  GCG_HIP_CHECK(pk.alloc(P * sizeof(uint64_t), st));
-  GCG_HIP_CHECK(pk2.alloc(P * sizeof(uint64_t), st));
-  GCG_HIP_CHECK(ucnt.alloc(sizeof(int64_t), st));
+  // 4 needs the pairs' keys, their sorted copy and hipcub's temporary to dedupe them
+  const uint64_t N = static_cast<uint64_t>(n_targets);
+  const int pair_bits = bits_to_hold(N * N);
+  int32_t* tlist = nullptr;
+  uint64_t *pk = nullptr, *pk2 = nullptr;
+  int64_t* ucnt = nullptr;
+  Tmp tmp2;
+  TmpSize ts2;
+  ts2.add(GCG_CUB(DeviceRadixSort::SortKeys, pk, pk2, static_cast<int>(P), 0, pair_bits));
+  ts2.add(GCG_CUB(DeviceSelect::Unique, pk2, pk, ucnt, static_cast<int>(P)));
+  if (gcg_status rc = ts2.status(fn)) return rc;
+  DevMem mem2;
+  GCG_HIP_CHECK(alloc_carved(mem2, st, [&](Carver& cv) {
+    tlist = cv.take<int32_t>(n_tlist);
+    pk = cv.take<uint64_t>(P);
+    pk2 = cv.take<uint64_t>(P);
+    ucnt = cv.take<int64_t>(1);
+    tmp2 = {cv.take<char>(ts2.bytes), ts2.bytes};
+  }));
   hipLaunchKernelGGL(target_fill_kernel, dim3(grid_for(n_nodes)), dim3(256), 0, st, n_targets, n_nodes,
-                     ptr.as<int64_t>(), keys.as<uint64_t>(), tcount.as<int64_t>(), toff.as<int64_t>(),
-                     tlist.as<int32_t>());
+                     ptr, keys, tcount, toff, tlist);
   hipLaunchKernelGGL(pair_keys_kernel, dim3(grid_for(P)), dim3(256), 0, st, n_nodes, n_targets, P,
-                     poff.as<int64_t>(), tcount.as<int64_t>(), toff.as<int64_t>(), tlist.as<int32_t>(),
-                     pk.as<uint64_t>());
+                     poff, tcount, toff, tlist, pk);
   GCG_HIP_CHECK(hipGetLastError());
   // 4. dedupe pairs
-  const uint64_t N = static_cast<uint64_t>(n_targets);
-  size_t t4 = 0, t5 = 0;
-  {
-    uint64_t* k = nullptr; int64_t* c = nullptr;
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, t4, k, k, static_cast<int>(P), 0, key_bits(N * N)));
-    GCG_HIP_CHECK(hipcub::DeviceSelect::Unique(nullptr, t5, k, k, c, static_cast<int>(P)));
-  }
-  GCG_HIP_CHECK(tmp2.alloc(std::max(t4, t5), st));
-  t4 = std::max(t4, t5);
-  size_t tt = t4;
-  GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(tmp2.p, tt, pk.as<uint64_t>(), pk2.as<uint64_t>(),
-                                                  static_cast<int>(P), 0, key_bits(N * N), st));
-  tt = t4;
-  GCG_HIP_CHECK(hipcub::DeviceSelect::Unique(tmp2.p, tt, pk2.as<uint64_t>(), pk.as<uint64_t>(),
-                                             ucnt.as<int64_t>(), static_cast<int>(P), st));
+  GCG_HIP_CHECK(tmp2.run(GCG_CUB(DeviceRadixSort::SortKeys, pk, pk2, static_cast<int>(P), 0, pair_bits, st)));
+  GCG_HIP_CHECK(tmp2.run(GCG_CUB(DeviceSelect::Unique, pk2, pk, ucnt, static_cast<int>(P), st)));
   int64_t n_unique = 0;
-  GCG_HIP_CHECK(hipMemcpyAsync(&n_unique, ucnt.p, 8, hipMemcpyDeviceToHost, st));
+  GCG_HIP_CHECK(hipMemcpyAsync(&n_unique, ucnt, 8, hipMemcpyDeviceToHost, st));
   GCG_HIP_CHECK(hipStreamSynchronize(st));
   if (n_unique > capacity)
     return fail(GCG_ERR_WORKSPACE, "output capacity %lld < %lld edges", (long long)capacity, (long long)n_unique);
-  hipLaunchKernelGGL(decode_pairs_kernel, dim3(grid_for(n_unique)), dim3(256), 0, st, n_targets,
-                     pk.as<uint64_t>(), ucnt.as<int64_t>(), out_u, out_v);
+  hipLaunchKernelGGL(decode_pairs_kernel, dim3(grid_for(n_unique)), dim3(256), 0, st, n_targets, pk, ucnt,
+                     out_u, out_v);
   GCG_HIP_CHECK(hipGetLastError());
   GCG_HIP_CHECK(hipStreamSynchronize(st));
   *n_edges = n_unique;
   return GCG_OK;
 }
-
 
 }  // extern "C"

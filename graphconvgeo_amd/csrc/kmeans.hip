@@ -13,7 +13,7 @@
 #include <climits>
 #include <cmath>
 
-#include "common.h"
+#include "scratch.h"
 #include "segment_kernels.h"
 
 using namespace gcg;
@@ -402,41 +402,25 @@ __global__ __launch_bounds__(256) void pp_select_kernel(int64_t N, int64_t nb,
   }
 }
 
-struct Carver {
-  char* p;
-  size_t used = 0;
-  explicit Carver(void* base) : p(static_cast<char*>(base)) {}
-  template <typename T> T* take(size_t n) {
-    T* out = p ? reinterpret_cast<T*>(p + used) : nullptr;
-    used += align_up(std::max<size_t>(n, 1) * sizeof(T), 256);
-    return out;
-  }
-};
-
-// The scratch of the label sort: keys, sorted keys, ids, sorted ids, ptr[C + 1], hipcub's.
+// The scratch of the label sort.
 struct SortSpace {
   int32_t *keys, *keys_sorted, *iota, *ids, *ptr;
-  void* tmp;
-  size_t tmp_bytes, total;
+  Tmp tmp;
+  size_t total;
 };
 
-gcg_status sort_space(int64_t N, int64_t C, void* workspace, SortSpace* s) {
-  size_t t = 0;
-  if (N > 0) {
-    int32_t* v = nullptr;
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, t, v, v, v, v, static_cast<int>(N),
-                                                     0, bits_for(C)));
-  }
+gcg_status sort_space(const char* fn, int64_t N, int64_t C, void* workspace, SortSpace* s) {
   Carver cv(workspace);
   s->keys = cv.take<int32_t>(N);
   s->keys_sorted = cv.take<int32_t>(N);
   s->iota = cv.take<int32_t>(N);
   s->ids = cv.take<int32_t>(N);
   s->ptr = cv.take<int32_t>(C + 1);
-  s->tmp = cv.take<char>(t);
-  s->tmp_bytes = t;
-  s->total = cv.used;
-  return GCG_OK;
+  TmpSize ts;
+  if (N > 0)
+    ts.add(GCG_CUB(DeviceRadixSort::SortPairs, s->keys, s->keys_sorted, s->iota, s->ids, static_cast<int>(N),
+        0, bits_to_count(C)));
+  return ts.take(fn, cv, &s->tmp, &s->total);
 }
 
 // ids = the point indices grouped by label, ascending inside a label (a stable sort of
@@ -447,10 +431,8 @@ gcg_status sort_by_label(int64_t N, int64_t C, const int32_t* labels, const Sort
     hipLaunchKernelGGL(label_keys_kernel, dim3(grid_for(N)), dim3(256), 0, st, N, C, labels,
                        s.keys, s.iota, status_dev);
     GCG_HIP_CHECK(hipGetLastError());
-    size_t t = s.tmp_bytes;
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(s.tmp, t, s.keys, s.keys_sorted, s.iota,
-                                                     s.ids, static_cast<int>(N), 0, bits_for(C),
-                                                     st));
+    GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceRadixSort::SortPairs, s.keys, s.keys_sorted, s.iota, s.ids,
+        static_cast<int>(N), 0, bits_to_count(C), st)));
   }
   hipLaunchKernelGGL(class_ptr_kernel, dim3(grid_for(N + 1)), dim3(256), 0, st, N, C,
                      s.keys_sorted, s.ptr);
@@ -509,9 +491,8 @@ gcg_status gcg_kmeans_assign_f64(int64_t N, const double* locs, int64_t C, const
   if (inertia_dev != nullptr) {
     size_t need = 0;
     (void)gcg_kmeans_assign_f64_workspace_bytes(N, &need);
-    if (workspace == nullptr || workspace_bytes < need)
-      return fail(GCG_ERR_WORKSPACE, "gcg_kmeans_assign_f64: workspace of %zu bytes, %zu needed",
-                  workspace_bytes, need);
+    if (gcg_status s = check_workspace("gcg_kmeans_assign_f64", workspace, workspace_bytes, need, 8))
+      return s;
     partials = static_cast<double*>(workspace);
   }
   hipLaunchKernelGGL(kmeans_assign_kernel, dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, N, C,
@@ -528,7 +509,7 @@ gcg_status gcg_kmeans_update_f64_workspace_bytes(int64_t N, int64_t C, size_t* b
   if (bytes == nullptr || !sizes_ok(N, C))
     return fail(GCG_ERR_INVALID_ARG, "gcg_kmeans_update_f64_workspace_bytes: bad sizes or null bytes");
   SortSpace s;
-  gcg_status rc = sort_space(N, C, nullptr, &s);
+  gcg_status rc = sort_space("gcg_kmeans_update_f64_workspace_bytes", N, C, nullptr, &s);
   if (rc != GCG_OK) return rc;
   *bytes = s.total;
   return GCG_OK;
@@ -554,11 +535,9 @@ gcg_status gcg_kmeans_update_f64(int64_t N, const double* locs, const int32_t* l
       !aligned(labels, 4) || !aligned(counts, 4) || !aligned(workspace, 256))
     return fail(GCG_ERR_MISALIGNED, "gcg_kmeans_update_f64: operand not aligned (workspace: 256 B)");
   SortSpace s;
-  gcg_status rc = sort_space(N, C, workspace, &s);
+  gcg_status rc = sort_space("gcg_kmeans_update_f64", N, C, workspace, &s);
   if (rc != GCG_OK) return rc;
-  if (workspace == nullptr || workspace_bytes < s.total)
-    return fail(GCG_ERR_WORKSPACE, "gcg_kmeans_update_f64: workspace of %zu bytes, %zu needed",
-                workspace_bytes, s.total);
+  if ((rc = check_workspace("gcg_kmeans_update_f64", workspace, workspace_bytes, s.total, 256))) return rc;
   rc = sort_by_label(N, C, labels, s, status_dev, st);
   if (rc != GCG_OK) return rc;
   hipLaunchKernelGGL(kmeans_update_kernel, dim3(segment_grid(C)), dim3(256), 0, st, C, locs, s.ptr,
@@ -590,9 +569,8 @@ gcg_status gcg_kmeans_pp_f64(int64_t N, const double* locs, int64_t C, const dou
     return fail(GCG_ERR_MISALIGNED, "gcg_kmeans_pp_f64: operand not aligned (workspace: 256 B)");
   size_t need = 0;
   (void)gcg_kmeans_pp_f64_workspace_bytes(N, &need);
-  if (workspace == nullptr || workspace_bytes < need)
-    return fail(GCG_ERR_WORKSPACE, "gcg_kmeans_pp_f64: workspace of %zu bytes, %zu needed",
-                workspace_bytes, need);
+  if (gcg_status s = check_workspace("gcg_kmeans_pp_f64", workspace, workspace_bytes, need, 256))
+    return s;
   Carver cv(workspace);
   double* d2 = cv.take<double>(N);
   const int64_t nb = pp_blocks(N);
@@ -638,11 +616,9 @@ gcg_status gcg_cluster_stats_f64(int64_t N, const double* locs, const int32_t* l
       !aligned(labels, 4) || !aligned(counts, 4) || !aligned(workspace, 256))
     return fail(GCG_ERR_MISALIGNED, "gcg_cluster_stats_f64: operand not aligned (workspace: 256 B)");
   SortSpace s;
-  gcg_status rc = sort_space(N, C, workspace, &s);
+  gcg_status rc = sort_space("gcg_cluster_stats_f64", N, C, workspace, &s);
   if (rc != GCG_OK) return rc;
-  if (workspace == nullptr || workspace_bytes < s.total)
-    return fail(GCG_ERR_WORKSPACE, "gcg_cluster_stats_f64: workspace of %zu bytes, %zu needed",
-                workspace_bytes, s.total);
+  if ((rc = check_workspace("gcg_cluster_stats_f64", workspace, workspace_bytes, s.total, 256))) return rc;
   rc = sort_by_label(N, C, labels, s, status_dev, st);
   if (rc != GCG_OK) return rc;
   hipLaunchKernelGGL(cluster_stats_kernel, dim3(segment_grid(C)), dim3(256), 0, st, C, locs, s.ptr,

@@ -5,7 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include "common.h"
+#include "scratch.h"
 #include "philox.h"
 
 using namespace gcg;
@@ -169,24 +169,27 @@ __global__ void mb_batch_bounds_kernel(int64_t n_batches, int64_t F,
   }
 }
 
-int key_bits(uint64_t max_key) {
-  int b = 1;
-  while (b < 32 && (uint64_t{1} << b) <= max_key) ++b;
-  return b;
-}
-
-struct SegLayout {
+// The scratch of the segmentation, in the order of the take calls. Two regions are shared on
+// purpose: the sort's key input is dead once the keys are sorted and then holds the run flags,
+// its payload input then holds the flags' running count.
+struct SegSpace {
   int64_t seg_cap;
   int end_bit;
-  size_t off_key_in, off_key_out, off_pay_in, off_pay_out, off_len, off_sel, off_seg_key, off_nseg,
-      off_tmp;
-  size_t tmp_bytes, total;
+  uint32_t *key_in, *key_out;
+  uint64_t *pay_in, *pay_out;
+  int32_t *flag, *count;  // key_in | flag, pay_in | count
+  int32_t *len, *sel_ptr;
+  uint32_t* seg_key;
+  int32_t* n_seg;
+  Tmp tmp;
+  size_t total;
 };
 
-// Workspace: [key_in | flags][key_out][payload_in | counts][payload_out][row lengths][sel_ptr]
-// [seg_key][n_seg][hipcub temporary].
-gcg_status seg_layout(const char* fn, int64_t n_sel, int64_t batch, int64_t F, int64_t nnz_sel,
-                      SegLayout* L) {
+// The arguments, then the fixed arrays (plain arithmetic, no HIP device), then with `sized` the
+// hipcub temporary behind them: rocPRIM sizes it for the device's architecture, so that half
+// needs a HIP device. A null workspace is the sizing pass.
+gcg_status seg_space(const char* fn, int64_t n_sel, int64_t batch, int64_t F, int64_t nnz_sel,
+                     void* workspace, bool sized, SegSpace* s) {
   if (n_sel < 0 || batch <= 0 || F <= 0 || nnz_sel < 0 || n_sel % batch != 0)
     return fail(GCG_ERR_INVALID_ARG, "%s: bad sizes n_sel=%lld batch=%lld n_cols=%lld nnz_sel=%lld "
                 "(n_sel must be a multiple of batch)", fn, static_cast<long long>(n_sel),
@@ -199,44 +202,33 @@ gcg_status seg_layout(const char* fn, int64_t n_sel, int64_t batch, int64_t F, i
     return fail(GCG_ERR_INVALID_ARG, "%s: %lld batches x %lld columns (or %lld entries) do not fit "
                 "the 32-bit sort key", fn, static_cast<long long>(nb), static_cast<long long>(F),
                 static_cast<long long>(nnz_sel));
-  L->seg_cap = std::min<int64_t>(nnz_sel, nb * F) + 1;
-  L->end_bit = key_bits(static_cast<uint64_t>(nb) * static_cast<uint64_t>(F));
-  const size_t n4 = align_up(static_cast<size_t>(nnz_sel) * 4, 256);
-  const size_t n8 = align_up(static_cast<size_t>(nnz_sel) * 8, 256);
-  size_t o = 0;
-  L->off_key_in = o;  o += n4;
-  L->off_key_out = o; o += n4;
-  L->off_pay_in = o;  o += n8;
-  L->off_pay_out = o; o += n8;
-  L->off_len = o;     o += align_up(static_cast<size_t>(n_sel + 1) * 4, 256);
-  L->off_sel = o;     o += align_up(static_cast<size_t>(n_sel + 1) * 4, 256);
-  L->off_seg_key = o; o += align_up(static_cast<size_t>(L->seg_cap) * 4, 256);
-  L->off_nseg = o;    o += 256;
-  L->off_tmp = o;
-  L->tmp_bytes = 0;
-  L->total = o;
-  return GCG_OK;
-}
-
-// The hipcub temporary behind the fixed arrays. rocPRIM sizes it for the device's architecture,
-// so this half needs a HIP device (the fixed half above is plain arithmetic).
-gcg_status seg_layout_tmp(const char* fn, int64_t n_sel, int64_t nnz_sel, SegLayout* L) {
-  size_t t_sort = 0, t_scan1 = 0, t_scan2 = 0;
+  s->seg_cap = std::min<int64_t>(nnz_sel, nb * F) + 1;
+  // nb * F is below 2^32 here (rejected above otherwise), so this never exceeds 32 bits
+  s->end_bit = bits_to_hold(static_cast<uint64_t>(nb) * static_cast<uint64_t>(F));
+  // take_exact throughout: an empty selection has empty arrays
+  Carver cv(workspace);
+  s->key_in = cv.take_exact<uint32_t>(nnz_sel);
+  s->key_out = cv.take_exact<uint32_t>(nnz_sel);
+  s->pay_in = cv.take_exact<uint64_t>(nnz_sel);
+  s->pay_out = cv.take_exact<uint64_t>(nnz_sel);
+  s->flag = reinterpret_cast<int32_t*>(s->key_in);
+  s->count = reinterpret_cast<int32_t*>(s->pay_in);
+  s->len = cv.take_exact<int32_t>(n_sel + 1);
+  s->sel_ptr = cv.take_exact<int32_t>(n_sel + 1);
+  s->seg_key = cv.take_exact<uint32_t>(s->seg_cap);
+  s->n_seg = cv.take_exact<int32_t>(1);
   const int n = static_cast<int>(std::max<int64_t>(nnz_sel, 1));
-  hipError_t e = hipcub::DeviceRadixSort::SortPairs(
-      nullptr, t_sort, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr),
-      static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr), n, 0, L->end_bit);
-  if (e == hipSuccess)
-    e = hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan1, static_cast<const int32_t*>(nullptr),
-                                         static_cast<int32_t*>(nullptr),
-                                         static_cast<int>(n_sel + 1));
-  if (e == hipSuccess)
-    e = hipcub::DeviceScan::InclusiveSum(nullptr, t_scan2, static_cast<const int32_t*>(nullptr),
-                                         static_cast<int32_t*>(nullptr), n);
-  if (e != hipSuccess) return fail(GCG_ERR_HIP, "%s: hipcub sizing: %s", fn, hipGetErrorString(e));
-  L->tmp_bytes = std::max(t_sort, std::max(t_scan1, t_scan2));
-  L->total = L->off_tmp + align_up(L->tmp_bytes, 256);
-  return GCG_OK;
+  // (the scans are sized through a const input, as they always were: the library keeps that
+  // instantiation of rocPRIM's kernels)
+  auto in = [](const int32_t* p) { return p; };
+  TmpSize ts;
+  if (sized) {
+    ts.add(GCG_CUB(DeviceRadixSort::SortPairs, s->key_in, s->key_out, s->pay_in, s->pay_out, n, 0,
+        s->end_bit));
+    ts.add(GCG_CUB(DeviceScan::ExclusiveSum, in(s->len), s->sel_ptr, static_cast<int>(n_sel + 1)));
+    ts.add(GCG_CUB(DeviceScan::InclusiveSum, in(s->flag), s->count, n));
+  }
+  return ts.take_exact(fn, cv, &s->tmp, &s->total);
 }
 
 // ---- the W1 step ------------------------------------------------------------------------
@@ -368,20 +360,17 @@ gcg_status segment_impl(const char* fn, int64_t n_rows, int64_t n_cols, const in
                         const DropKey* drop, const int32_t* step_dev, float* vals_drop) {
   if (n_rows < 0 || n_rows >= INT32_MAX)
     return fail(GCG_ERR_INVALID_ARG, "%s: bad n_rows", fn);
-  SegLayout L;
-  if (gcg_status s = seg_layout(fn, n_sel, batch, n_cols, nnz_sel, &L)) return s;
+  SegSpace s;
+  if (gcg_status rc = seg_space(fn, n_sel, batch, n_cols, nnz_sel, workspace, false, &s)) return rc;
   if (indptr == nullptr || batch_seg_ptr == nullptr || seg_col == nullptr || seg_ptr == nullptr ||
       (n_sel > 0 && perm == nullptr) ||
       (nnz_sel > 0 && (indices == nullptr || vals == nullptr || ent_pos == nullptr ||
                        ent_val == nullptr)))
     return fail(GCG_ERR_INVALID_ARG, "%s: NULL buffer", fn);
   // the fixed arrays first (host arithmetic), then the whole with the hipcub temporary
-  if (workspace == nullptr || workspace_bytes < L.total)
-    return fail(GCG_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, L.total);
-  if (!aligned(workspace, 8)) return fail(GCG_ERR_MISALIGNED, "%s: workspace not 8-B aligned", fn);
-  if (gcg_status s = seg_layout_tmp(fn, n_sel, nnz_sel, &L)) return s;
-  if (workspace_bytes < L.total)
-    return fail(GCG_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, L.total);
+  if (gcg_status rc = check_workspace(fn, workspace, workspace_bytes, s.total, 8)) return rc;
+  if (gcg_status rc = seg_space(fn, n_sel, batch, n_cols, nnz_sel, workspace, true, &s)) return rc;
+  if (gcg_status rc = check_workspace(fn, workspace, workspace_bytes, s.total, 8)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t nb = n_sel / batch;
   if (nnz_sel == 0) {  // no entry: every batch's range is empty
@@ -389,54 +378,41 @@ gcg_status segment_impl(const char* fn, int64_t n_rows, int64_t n_cols, const in
     GCG_HIP_CHECK(hipMemsetAsync(seg_ptr, 0, sizeof(int32_t), st));
     return GCG_OK;
   }
-  char* w = static_cast<char*>(workspace);
-  uint32_t* key_in = reinterpret_cast<uint32_t*>(w + L.off_key_in);
-  uint32_t* key_out = reinterpret_cast<uint32_t*>(w + L.off_key_out);
-  uint64_t* pay_in = reinterpret_cast<uint64_t*>(w + L.off_pay_in);
-  uint64_t* pay_out = reinterpret_cast<uint64_t*>(w + L.off_pay_out);
-  int32_t* sel_ptr = reinterpret_cast<int32_t*>(w + L.off_sel);
-  uint32_t* seg_key = reinterpret_cast<uint32_t*>(w + L.off_seg_key);
-  int32_t* n_seg = reinterpret_cast<int32_t*>(w + L.off_nseg);
-  void* tmp = w + L.off_tmp;
-  size_t tb = L.tmp_bytes;
   const uint32_t sentinel = static_cast<uint32_t>(nb * n_cols);
   const int n = static_cast<int>(nnz_sel);
 
-  int32_t* len = reinterpret_cast<int32_t*>(w + L.off_len);
   hipLaunchKernelGGL(mb_row_len_kernel, dim3(grid_for(n_sel + 1)), dim3(256), 0, st, n_rows, indptr,
-                     perm, n_sel, len);
+                     perm, n_sel, s.len);
   GCG_HIP_CHECK(hipGetLastError());
-  GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, len, sel_ptr,
-                                                 static_cast<int>(n_sel + 1), st));
+  GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceScan::ExclusiveSum, s.len, s.sel_ptr, static_cast<int>(n_sel + 1),
+      st)));
   const int64_t row_blocks = (n_sel + kWavesPerBlock - 1) / kWavesPerBlock;
   const dim3 expand_grid(
       static_cast<unsigned>(std::min<int64_t>(std::max<int64_t>(row_blocks, 1), 1 << 20)));
   if (drop == nullptr)
     hipLaunchKernelGGL(mb_expand_kernel, expand_grid, dim3(kBlock), 0, st, n_rows, n_cols, indptr,
-                       indices, vals, perm, n_sel, batch, nnz_sel, sentinel, sel_ptr, key_in, pay_in);
+                       indices, vals, perm, n_sel, batch, nnz_sel, sentinel, s.sel_ptr, s.key_in,
+                       s.pay_in);
   else
     hipLaunchKernelGGL(mb_expand_dropout_kernel, expand_grid, dim3(kBlock), 0, st, n_rows, n_cols,
-                       indptr, indices, vals, perm, n_sel, batch, nnz_sel, sentinel, sel_ptr,
-                       key_in, pay_in, *drop, step_dev, vals_drop);
+                       indptr, indices, vals, perm, n_sel, batch, nnz_sel, sentinel, s.sel_ptr,
+                       s.key_in, s.pay_in, *drop, step_dev, vals_drop);
   GCG_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(mb_tail_kernel, dim3(64), dim3(256), 0, st, sel_ptr, n_sel, nnz_sel, sentinel,
-                     key_in, pay_in);
+  hipLaunchKernelGGL(mb_tail_kernel, dim3(64), dim3(256), 0, st, s.sel_ptr, n_sel, nnz_sel,
+                     sentinel, s.key_in, s.pay_in);
   GCG_HIP_CHECK(hipGetLastError());
-  tb = L.tmp_bytes;
-  GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key_in, key_out, pay_in, pay_out, n, 0,
-                                                   L.end_bit, st));
-  int32_t* flag = reinterpret_cast<int32_t*>(key_in);
-  int32_t* count = reinterpret_cast<int32_t*>(pay_in);
-  hipLaunchKernelGGL(mb_unpack_kernel, dim3(grid_for(nnz_sel)), dim3(256), 0, st, nnz_sel, key_out,
-                     pay_out, ent_pos, ent_val, flag);
+  GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceRadixSort::SortPairs, s.key_in, s.key_out, s.pay_in, s.pay_out, n, 0,
+      s.end_bit, st)));
+  // from here key_in and pay_in are dead: their regions hold the run flags and their count
+  hipLaunchKernelGGL(mb_unpack_kernel, dim3(grid_for(nnz_sel)), dim3(256), 0, st, nnz_sel,
+                     s.key_out, s.pay_out, ent_pos, ent_val, s.flag);
   GCG_HIP_CHECK(hipGetLastError());
-  tb = L.tmp_bytes;
-  GCG_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(tmp, tb, flag, count, n, st));
+  GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceScan::InclusiveSum, s.flag, s.count, n, st)));
   hipLaunchKernelGGL(mb_segments_kernel, dim3(grid_for(nnz_sel)), dim3(256), 0, st, nnz_sel, n_cols,
-                     L.seg_cap, key_out, flag, count, seg_key, seg_col, seg_ptr, n_seg);
+                     s.seg_cap, s.key_out, s.flag, s.count, s.seg_key, seg_col, seg_ptr, s.n_seg);
   GCG_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(mb_batch_bounds_kernel, dim3(grid_for(nb + 1)), dim3(256), 0, st, nb, n_cols,
-                     seg_key, n_seg, batch_seg_ptr);
+                     s.seg_key, s.n_seg, batch_seg_ptr);
   GCG_HIP_CHECK(hipGetLastError());
   return GCG_OK;
 }
@@ -448,14 +424,13 @@ extern "C" {
 gcg_status gcg_minibatch_segment_sizes(int64_t n_sel, int64_t batch, int64_t n_cols,
                                        int64_t nnz_sel, int64_t* seg_capacity,
                                        size_t* workspace_bytes) {
-  SegLayout L;
-  if (gcg_status s = seg_layout("gcg_minibatch_segment_sizes", n_sel, batch, n_cols, nnz_sel, &L))
-    return s;
-  if (seg_capacity != nullptr) *seg_capacity = L.seg_cap;
-  if (workspace_bytes != nullptr) {
-    if (gcg_status s = seg_layout_tmp("gcg_minibatch_segment_sizes", n_sel, nnz_sel, &L)) return s;
-    *workspace_bytes = L.total;
-  }
+  const char* fn = "gcg_minibatch_segment_sizes";
+  SegSpace s;
+  // the capacity alone needs no HIP device
+  if (gcg_status rc = seg_space(fn, n_sel, batch, n_cols, nnz_sel, nullptr, workspace_bytes != nullptr, &s))
+    return rc;
+  if (seg_capacity != nullptr) *seg_capacity = s.seg_cap;
+  if (workspace_bytes != nullptr) *workspace_bytes = s.total;
   return GCG_OK;
 }
 

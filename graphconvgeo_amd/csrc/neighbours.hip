@@ -17,7 +17,7 @@
 #include <climits>
 #include <cmath>
 
-#include "common.h"
+#include "scratch.h"
 #include "segment_kernels.h"
 
 using namespace gcg;
@@ -475,17 +475,6 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(int64_t ncand, int64_t p
 }
 
 // ---- host side --------------------------------------------------------------------------------
-struct Carver {
-  char* p;
-  size_t used = 0;
-  explicit Carver(void* base) : p(static_cast<char*>(base)) {}
-  template <typename T> T* take(size_t n) {
-    T* out = p ? reinterpret_cast<T*>(p + used) : nullptr;
-    used += align_up(std::max<size_t>(n, 1) * sizeof(T), 256);
-    return out;
-  }
-};
-
 constexpr int64_t kMaxRows = INT32_MAX - 1;
 constexpr int64_t kMaxQueries = int64_t{65535} * kQueryTileSmall;  // grid.y
 
@@ -499,18 +488,11 @@ int64_t merge_splits(int64_t ncand) {
 struct RankSpace {
   int32_t *sptr, *pair_q, *iota, *sperm, *slot;
   uint64_t *key, *skey;
-  void* tmp;
-  size_t tmp_bytes, total;
+  Tmp tmp;
+  size_t total;
 };
 
-gcg_status rank_space(int64_t Q, int64_t P, void* workspace, RankSpace* s) {
-  size_t t = 0;
-  if (P > 0 && Q > 0) {
-    uint64_t* k = nullptr;
-    int32_t* v = nullptr;
-    GCG_HIP_CHECK(hipcub::DeviceSegmentedRadixSort::SortPairs(
-        nullptr, t, k, k, v, v, static_cast<int>(P), static_cast<int>(Q), v, v));
-  }
+gcg_status rank_space(const char* fn, int64_t Q, int64_t P, void* workspace, RankSpace* s) {
   Carver cv(workspace);
   s->sptr = cv.take<int32_t>(Q + 1);
   s->pair_q = cv.take<int32_t>(P);
@@ -519,10 +501,11 @@ gcg_status rank_space(int64_t Q, int64_t P, void* workspace, RankSpace* s) {
   s->slot = cv.take<int32_t>(P);
   s->key = cv.take<uint64_t>(P);
   s->skey = cv.take<uint64_t>(P);
-  s->tmp = cv.take<char>(t);
-  s->tmp_bytes = t;
-  s->total = cv.used;
-  return GCG_OK;
+  TmpSize ts;
+  if (P > 0 && Q > 0)
+    ts.add(GCG_CUB(DeviceSegmentedRadixSort::SortPairs, s->key, s->skey, s->iota, s->sperm,
+        static_cast<int>(P), static_cast<int>(Q), s->sptr, s->sptr));
+  return ts.take(fn, cv, &s->tmp, &s->total);
 }
 
 bool matrix_ok(int64_t rows, int64_t D, int64_t ld) { return rows >= 0 && D >= 1 && ld >= D; }
@@ -576,9 +559,8 @@ gcg_status gcg_minmax_l1_rows_f32(int64_t V, int64_t D, const float* E, int64_t 
     return fail(GCG_ERR_MISALIGNED, "gcg_minmax_l1_rows_f32: operand not aligned (workspace: 256 B)");
   size_t need = 0;
   (void)gcg_minmax_l1_rows_f32_workspace_bytes(V, D, &need);
-  if (workspace == nullptr || workspace_bytes < need)
-    return fail(GCG_ERR_WORKSPACE, "gcg_minmax_l1_rows_f32: workspace of %zu bytes, %zu needed",
-                workspace_bytes, need);
+  if (gcg_status s = check_workspace("gcg_minmax_l1_rows_f32", workspace, workspace_bytes, need, 256))
+    return s;
   const int64_t nb = minmax_blocks(V);
   Carver cv(workspace);
   float* pmin = cv.take<float>(nb * D);
@@ -602,7 +584,7 @@ gcg_status gcg_neighbour_ranks_f32_workspace_bytes(int64_t Q, int64_t P, size_t*
   if (bytes == nullptr || Q < 0 || Q > kMaxQueries || P < 0 || P > INT32_MAX - 1)
     return fail(GCG_ERR_INVALID_ARG, "gcg_neighbour_ranks_f32_workspace_bytes: bad sizes or null bytes");
   RankSpace s;
-  gcg_status rc = rank_space(Q, P, nullptr, &s);
+  gcg_status rc = rank_space("gcg_neighbour_ranks_f32_workspace_bytes", Q, P, nullptr, &s);
   if (rc != GCG_OK) return rc;
   *bytes = s.total;
   return GCG_OK;
@@ -630,11 +612,10 @@ gcg_status gcg_neighbour_ranks_f32(int64_t V, int64_t D, const float* E, int64_t
       !aligned(rank, 4) || !aligned(workspace, 256))
     return fail(GCG_ERR_MISALIGNED, "gcg_neighbour_ranks_f32: operand not aligned (workspace: 256 B)");
   RankSpace s;
-  gcg_status rc = rank_space(Q, P, workspace, &s);
+  gcg_status rc = rank_space("gcg_neighbour_ranks_f32", Q, P, workspace, &s);
   if (rc != GCG_OK) return rc;
-  if (workspace == nullptr || workspace_bytes < s.total)
-    return fail(GCG_ERR_WORKSPACE, "gcg_neighbour_ranks_f32: workspace of %zu bytes, %zu needed",
-                workspace_bytes, s.total);
+  if ((rc = check_workspace("gcg_neighbour_ranks_f32", workspace, workspace_bytes, s.total, 256)))
+    return rc;
   GCG_HIP_CHECK(hipMemsetAsync(rank, 0, P * sizeof(int32_t), st));
   GCG_HIP_CHECK(hipMemsetAsync(s.slot, 0, P * sizeof(int32_t), st));
   GCG_HIP_CHECK(hipMemsetAsync(s.pair_q, 0xff, P * sizeof(int32_t), st));
@@ -646,10 +627,8 @@ gcg_status gcg_neighbour_ranks_f32(int64_t V, int64_t D, const float* E, int64_t
                      queries, ldq, P, s.pair_q, pair_word, s.key, status_dev);
   hipLaunchKernelGGL(iota_kernel, dim3(grid_for(P)), dim3(256), 0, st, P, s.iota);
   GCG_HIP_CHECK(hipGetLastError());
-  size_t t = s.tmp_bytes;
-  GCG_HIP_CHECK(hipcub::DeviceSegmentedRadixSort::SortPairs(
-      s.tmp, t, s.key, s.skey, s.iota, s.sperm, static_cast<int>(P), static_cast<int>(Q), s.sptr,
-      s.sptr + 1, 0, 64, st));
+  GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceSegmentedRadixSort::SortPairs, s.key, s.skey, s.iota, s.sperm,
+      static_cast<int>(P), static_cast<int>(Q), s.sptr, s.sptr + 1, 0, 64, st)));
   const bool vec = can_vectorize(E, lde);
   if (Q <= kQueryTileSmall) {
     hipLaunchKernelGGL(neighbour_count_kernel<kQueryTileSmall>,
@@ -703,9 +682,8 @@ gcg_status gcg_kneighbors_f32(int64_t V, int64_t D, const float* E, int64_t lde,
     return fail(GCG_ERR_MISALIGNED, "gcg_kneighbors_f32: operand not aligned (workspace: 256 B)");
   size_t need = 0;
   (void)gcg_kneighbors_f32_workspace_bytes(V, Q, k, &need);
-  if (workspace == nullptr || workspace_bytes < need)
-    return fail(GCG_ERR_WORKSPACE, "gcg_kneighbors_f32: workspace of %zu bytes, %zu needed",
-                workspace_bytes, need);
+  if (gcg_status s = check_workspace("gcg_kneighbors_f32", workspace, workspace_bytes, need, 256))
+    return s;
   const int kk = static_cast<int>(std::min<int64_t>(k, kRowTile));
   const int64_t nt = row_tiles(V);
   const int64_t ncand = nt * kk, nsplit = merge_splits(ncand);

@@ -7,7 +7,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "common.h"
+#include "scratch.h"
 #include "index_kernels.h"
 
 using namespace gcg;
@@ -117,13 +117,6 @@ __global__ void row_products_kernel(int64_t m, const int32_t* __restrict__ a_ptr
     row_off[i] = j < nnz_a ? off[j] : total;
   }
 }
-
-struct DevBuf {
-  void* p = nullptr;
-  hipStream_t s = nullptr;
-  ~DevBuf() { if (p) (void)hipFreeAsync(p, s); }
-};
-
 
 // ---- row-wise SpGEMM with a dense LDS accumulator (the default for p <= 8 slabs) ---------
 // One 1024-thread workgroup per row of C, rows dispatched longest-first. The row's products
@@ -592,38 +585,31 @@ gcg_status spgemm_rows(int64_t m, int64_t p, int64_t nnz_a, const int32_t* a_ptr
   // The row kernels write C in the upper-bound layout (row i at rowoff[i]) straight into the
   // caller's capacity-P c_idx / c_val, which are then compacted in place: no products-sized
   // temporary (21 GB at Twitter-World) is allocated per call.
-  DevBuf b_key, b_key2, b_id, b_id2, b_kept, b_cp64, b_tmp;
-  size_t t_sort = 0, t_scan = 0;
-  {
-    uint32_t* k = nullptr; int32_t* v = nullptr; int64_t* o = nullptr;
-    if (hipcub::DeviceRadixSort::SortPairsDescending(nullptr, t_sort, k, k, v, v, static_cast<int>(m)) != hipSuccess ||
-        hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan, o, o, static_cast<int>(m + 1)) != hipSuccess)
-      return fail(GCG_ERR_HIP, "hipcub sizing failed");
-  }
-  auto alloc = [&](DevBuf& b, size_t bytes) -> hipError_t {
-    b.s = st;
-    return hipMallocAsync(&b.p, std::max<size_t>(bytes, 16), st);
-  };
-  hipError_t e = alloc(b_key, m * sizeof(uint32_t));
-  if (e == hipSuccess) e = alloc(b_key2, m * sizeof(uint32_t));
-  if (e == hipSuccess) e = alloc(b_id, m * sizeof(int32_t));
-  if (e == hipSuccess) e = alloc(b_id2, m * sizeof(int32_t));
-  if (e == hipSuccess) e = alloc(b_kept, (m + 1) * sizeof(int64_t));
-  if (e == hipSuccess) e = alloc(b_cp64, (m + 1) * sizeof(int64_t));
-  if (e == hipSuccess) e = alloc(b_tmp, std::max(t_sort, t_scan));
+  uint32_t *key = nullptr, *key2 = nullptr;
+  int32_t *id = nullptr, *id2 = nullptr;
+  int64_t *kept = nullptr, *cp64 = nullptr;
+  Tmp tmp;
+  TmpSize ts;
+  ts.add(GCG_CUB(DeviceRadixSort::SortPairsDescending, key, key2, id, id2, static_cast<int>(m)));
+  ts.add(GCG_CUB(DeviceScan::ExclusiveSum, kept, cp64, static_cast<int>(m + 1)));
+  if (gcg_status rc = ts.status("gcg_spgemm")) return rc;
+  DevMem mem;
+  hipError_t e = alloc_carved(mem, st, [&](Carver& cv) {
+    key = cv.take<uint32_t>(m);
+    key2 = cv.take<uint32_t>(m);
+    id = cv.take<int32_t>(m);
+    id2 = cv.take<int32_t>(m);
+    kept = cv.take<int64_t>(m + 1);
+    cp64 = cv.take<int64_t>(m + 1);
+    tmp = {cv.take<char>(ts.bytes), ts.bytes};
+  });
   if (e != hipSuccess) return fail(GCG_ERR_ALLOC, "SpGEMM row temporaries: %s", hipGetErrorString(e));
-  auto* key = static_cast<uint32_t*>(b_key.p);
-  auto* key2 = static_cast<uint32_t*>(b_key2.p);
-  auto* id = static_cast<int32_t*>(b_id.p);
-  auto* id2 = static_cast<int32_t*>(b_id2.p);
-  auto* kept = static_cast<int64_t*>(b_kept.p);
-  auto* cp64 = static_cast<int64_t*>(b_cp64.p);
   const int small_ok = (p <= kSmallMaxCols && !(flags & GCG_SPGEMM_DENSE_SLABS)) ? 1 : 0;
   hipLaunchKernelGGL(row_products_u32_kernel, dim3(grid_for(m)), dim3(256), 0, st, m, rowoff_dev, a_ptr, small_ok,
                      key, id);
   GCG_HIP_CHECK(hipGetLastError());
-  size_t tb = t_sort;
-  GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairsDescending(b_tmp.p, tb, key, key2, id, id2, static_cast<int>(m), 0, 32, st));
+  GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceRadixSort::SortPairsDescending, key, key2, id, id2, static_cast<int>(m),
+      0, 32, st)));
   GCG_HIP_CHECK(hipMemsetAsync(kept + m, 0, sizeof(int64_t), st));
   // rows [0, n_big) of the longest-first order take the dense slabs, the rest the sort kernel
   std::vector<uint32_t> skey(m);
@@ -654,8 +640,7 @@ gcg_status spgemm_rows(int64_t m, int64_t p, int64_t nnz_a, const int32_t* a_ptr
                        tval, kept);
   const hipError_t launch_err = hipGetLastError();
   if (launch_err != hipSuccess) return fail(GCG_ERR_HIP, "SpGEMM row kernels: %s", hipGetErrorString(launch_err));
-  tb = t_scan;
-  GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(b_tmp.p, tb, kept, cp64, static_cast<int>(m + 1), st));
+  GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceScan::ExclusiveSum, kept, cp64, static_cast<int>(m + 1), st)));
   std::vector<int64_t> cptr(m + 1);
   GCG_HIP_CHECK(hipMemcpyAsync(cptr.data(), cp64, (m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   GCG_HIP_CHECK(hipStreamSynchronize(st));
@@ -668,12 +653,12 @@ gcg_status spgemm_rows(int64_t m, int64_t p, int64_t nnz_a, const int32_t* a_ptr
       hipLaunchKernelGGL(spgemm_compact_inplace_kernel, dim3(grid_for((rg.second - rg.first) * 64)), dim3(256), 0,
                          st, rg.first, rg.second, rowoff_dev, cp64, c_idx, c_val);
   } else {  // rows that merge few products: compact through an nnz(C)-sized temporary instead
-    DevBuf b_cidx, b_cval;
-    e = alloc(b_cidx, nnz_c * sizeof(int32_t));
-    if (e == hipSuccess) e = alloc(b_cval, nnz_c * sizeof(float));
+    DevMem b_cidx, b_cval;
+    e = b_cidx.alloc(nnz_c * sizeof(int32_t), st);
+    if (e == hipSuccess) e = b_cval.alloc(nnz_c * sizeof(float), st);
     if (e != hipSuccess) return fail(GCG_ERR_ALLOC, "SpGEMM compaction temporary: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(spgemm_compact_kernel, dim3(grid_for(m * 64)), dim3(256), 0, st, m, rowoff_dev, cp64,
-                       c_idx, c_val, c_ptr, static_cast<int32_t*>(b_cidx.p), static_cast<float*>(b_cval.p));
+                       c_idx, c_val, c_ptr, b_cidx.as<int32_t>(), b_cval.as<float>());
     GCG_HIP_CHECK(hipGetLastError());
     GCG_HIP_CHECK(hipMemcpyAsync(c_idx, b_cidx.p, nnz_c * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     GCG_HIP_CHECK(hipMemcpyAsync(c_val, b_cval.p, nnz_c * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -703,28 +688,23 @@ gcg_status spgemm_impl(int64_t m, int64_t n, int64_t p, int64_t nnz_a, const int
     return GCG_OK;
   }
   if (nnz_a > INT32_MAX) return fail(GCG_ERR_INVALID_ARG, "nnz(A) exceeds int32");
-  auto alloc = [&](DevBuf& b, size_t bytes) -> hipError_t {
-    b.s = st;
-    return hipMallocAsync(&b.p, std::max<size_t>(bytes, 16), st);
-  };
   // ---- products per nonzero / per row, row chunks (host) ----
-  DevBuf b_off, b_rowoff, b_tmp0;
-  size_t t_scan = 0;
-  {
-    int64_t* o = nullptr;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan, o, o, static_cast<int>(nnz_a)) != hipSuccess)
-      return fail(GCG_ERR_HIP, "hipcub sizing failed");
-  }
-  hipError_t e = alloc(b_off, nnz_a * sizeof(int64_t));
-  if (e == hipSuccess) e = alloc(b_rowoff, (m + 1) * sizeof(int64_t));
-  if (e == hipSuccess) e = alloc(b_tmp0, t_scan);
+  DevMem b_off, b_rowoff, b_tmp0;
+  TmpSize scan_size;
+  int64_t* off = nullptr;
+  scan_size.add(GCG_CUB(DeviceScan::ExclusiveSum, off, off, static_cast<int>(nnz_a)));
+  if (scan_size.err != hipSuccess)
+    return fail(GCG_ERR_HIP, "gcg_spgemm: hipcub sizing: %s", hipGetErrorString(scan_size.err));
+  hipError_t e = b_off.alloc(nnz_a * sizeof(int64_t), st);
+  if (e == hipSuccess) e = b_rowoff.alloc((m + 1) * sizeof(int64_t), st);
+  if (e == hipSuccess) e = b_tmp0.alloc(scan_size.bytes, st);
   if (e != hipSuccess) return fail(GCG_ERR_ALLOC, "SpGEMM row offsets: %s", hipGetErrorString(e));
-  auto* off = static_cast<int64_t*>(b_off.p);
-  auto* rowoff_dev = static_cast<int64_t*>(b_rowoff.p);
+  off = b_off.as<int64_t>();
+  auto* rowoff_dev = b_rowoff.as<int64_t>();
   hipLaunchKernelGGL(spgemm_count_kernel, dim3(grid_for(nnz_a)), dim3(256), 0, st, nnz_a, a_idx, b_ptr, off);
   GCG_HIP_CHECK(hipGetLastError());
-  size_t tb = t_scan;
-  GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(b_tmp0.p, tb, off, off, static_cast<int>(nnz_a), st));
+  const Tmp tmp0{b_tmp0.p, scan_size.bytes};
+  GCG_HIP_CHECK(tmp0.run(GCG_CUB(DeviceScan::ExclusiveSum, off, off, static_cast<int>(nnz_a), st)));
   hipLaunchKernelGGL(row_products_kernel, dim3(grid_for(m + 1)), dim3(256), 0, st, m, a_ptr, off, nnz_a,
                      n_products, rowoff_dev);
   GCG_HIP_CHECK(hipGetLastError());
@@ -761,48 +741,46 @@ gcg_status spgemm_impl(int64_t m, int64_t n, int64_t p, int64_t nnz_a, const int
   P_max = std::max<int64_t>(P_max, 1);
 
   // ---- temporaries sized for the largest chunk, reused ----
-  size_t t_sort = 0, t_sel = 0;
-  {
-    uint64_t* k = nullptr; int32_t* v = nullptr; int64_t* c = nullptr; int64_t* o = nullptr;
-    TACC* f = nullptr;
-    size_t t2 = 0, t3 = 0;
-    if (hipcub::DeviceRadixSort::SortPairs(nullptr, t_sort, k, k, v, v, static_cast<int>(P_max), 0, 64) != hipSuccess ||
-        hipcub::DeviceSelect::Flagged(nullptr, t_sel, k, v, k, c, static_cast<int>(P_max)) != hipSuccess ||
-        hipcub::DeviceSelect::Flagged(nullptr, t2, f, v, f, c, static_cast<int>(P_max)) != hipSuccess ||
-        hipcub::DeviceScan::ExclusiveSum(nullptr, t3, o, o, static_cast<int>(std::max<int64_t>(nnz_max, 1))) != hipSuccess)
-      return fail(GCG_ERR_HIP, "hipcub sizing failed");
-    t_sel = std::max({t_sel, t2, t3});
-  }
-  const size_t tmp_bytes = std::max({t_sort, t_sel, t_scan});
-  DevBuf b_cp, b_row, b_coff, b_keys, b_keys2, b_seq, b_seq2, b_prod, b_flags, b_starts, b_sums, b_tmp, b_cnt;
-  e = alloc(b_cp, (m_max + 1) * sizeof(int32_t));
-  if (e == hipSuccess) e = alloc(b_row, nnz_max * sizeof(int32_t));
-  if (e == hipSuccess) e = alloc(b_coff, nnz_max * sizeof(int64_t));
-  if (e == hipSuccess) e = alloc(b_keys, P_max * sizeof(uint64_t));
-  if (e == hipSuccess) e = alloc(b_keys2, P_max * sizeof(uint64_t));
-  if (e == hipSuccess) e = alloc(b_seq, P_max * sizeof(int32_t));
-  if (e == hipSuccess) e = alloc(b_seq2, P_max * sizeof(int32_t));
-  if (e == hipSuccess) e = alloc(b_prod, P_max * sizeof(TACC));
-  if (e == hipSuccess) e = alloc(b_flags, P_max * sizeof(int32_t));
-  if (e == hipSuccess) e = alloc(b_starts, P_max * sizeof(int32_t));
-  if (e == hipSuccess) e = alloc(b_sums, P_max * sizeof(TACC));
-  if (e == hipSuccess) e = alloc(b_tmp, tmp_bytes);
-  if (e == hipSuccess) e = alloc(b_cnt, 2 * sizeof(int64_t));
+  // (separate allocations on purpose: ~21 GB per chunk at Twitter-World need not be contiguous)
+  DevMem b_cp, b_row, b_coff, b_keys, b_keys2, b_seq, b_seq2, b_prod, b_flags, b_starts, b_sums, b_tmp, b_cnt;
+  e = b_cp.alloc((m_max + 1) * sizeof(int32_t), st);
+  if (e == hipSuccess) e = b_row.alloc(nnz_max * sizeof(int32_t), st);
+  if (e == hipSuccess) e = b_coff.alloc(nnz_max * sizeof(int64_t), st);
+  if (e == hipSuccess) e = b_keys.alloc(P_max * sizeof(uint64_t), st);
+  if (e == hipSuccess) e = b_keys2.alloc(P_max * sizeof(uint64_t), st);
+  if (e == hipSuccess) e = b_seq.alloc(P_max * sizeof(int32_t), st);
+  if (e == hipSuccess) e = b_seq2.alloc(P_max * sizeof(int32_t), st);
+  if (e == hipSuccess) e = b_prod.alloc(P_max * sizeof(TACC), st);
+  if (e == hipSuccess) e = b_flags.alloc(P_max * sizeof(int32_t), st);
+  if (e == hipSuccess) e = b_starts.alloc(P_max * sizeof(int32_t), st);
+  if (e == hipSuccess) e = b_sums.alloc(P_max * sizeof(TACC), st);
+  if (e == hipSuccess) e = b_cnt.alloc(2 * sizeof(int64_t), st);
   if (e != hipSuccess)
     return fail(GCG_ERR_ALLOC, "SpGEMM temporaries (%lld products per chunk): %s", (long long)P_max,
                 hipGetErrorString(e));
-  auto* cptr = static_cast<int32_t*>(b_cp.p);
-  auto* row_of = static_cast<int32_t*>(b_row.p);
-  auto* coff = static_cast<int64_t*>(b_coff.p);
-  auto* keys = static_cast<uint64_t*>(b_keys.p);
-  auto* keys2 = static_cast<uint64_t*>(b_keys2.p);
-  auto* seq = static_cast<int32_t*>(b_seq.p);
-  auto* seq2 = static_cast<int32_t*>(b_seq2.p);
-  auto* prod = static_cast<TACC*>(b_prod.p);
-  auto* flags = static_cast<int32_t*>(b_flags.p);
-  auto* starts = static_cast<int32_t*>(b_starts.p);
-  auto* sums = static_cast<TACC*>(b_sums.p);
-  auto* cnts = static_cast<int64_t*>(b_cnt.p);
+  auto* cptr = b_cp.as<int32_t>();
+  auto* row_of = b_row.as<int32_t>();
+  auto* coff = b_coff.as<int64_t>();
+  auto* keys = b_keys.as<uint64_t>();
+  auto* keys2 = b_keys2.as<uint64_t>();
+  auto* seq = b_seq.as<int32_t>();
+  auto* seq2 = b_seq2.as<int32_t>();
+  auto* prod = b_prod.as<TACC>();
+  auto* flags = b_flags.as<int32_t>();
+  auto* starts = b_starts.as<int32_t>();
+  auto* sums = b_sums.as<TACC>();
+  auto* cnts = b_cnt.as<int64_t>();
+  TmpSize ts = scan_size;
+  ts.add(GCG_CUB(DeviceRadixSort::SortPairs, keys, keys2, seq, seq2, static_cast<int>(P_max), 0, 64));
+  ts.add(GCG_CUB(DeviceSelect::Flagged, keys2, flags, keys, cnts, static_cast<int>(P_max)));
+  ts.add(GCG_CUB(DeviceSelect::Flagged, sums, flags, prod, cnts, static_cast<int>(P_max)));
+  ts.add(GCG_CUB(DeviceScan::ExclusiveSum, coff, coff, static_cast<int>(std::max<int64_t>(nnz_max, 1))));
+  if (gcg_status rc = ts.status("gcg_spgemm")) return rc;
+  e = b_tmp.alloc(ts.bytes, st);
+  if (e != hipSuccess)
+    return fail(GCG_ERR_ALLOC, "SpGEMM temporaries (%lld products per chunk): %s", (long long)P_max,
+                hipGetErrorString(e));
+  const Tmp tmp{b_tmp.p, ts.bytes};
 
   int64_t nnz_done = 0;
   for (size_t c = 0; c + 1 < cuts.size(); ++c) {
@@ -821,21 +799,18 @@ gcg_status spgemm_impl(int64_t m, int64_t n, int64_t p, int64_t nnz_a, const int
     hipLaunchKernelGGL(expand_rows_kernel, dim3(grid_for(mc)), dim3(256), 0, st, mc, cptr, row_of);
     hipLaunchKernelGGL(spgemm_count_kernel, dim3(grid_for(nnz_c)), dim3(256), 0, st, nnz_c, a_idx + base, b_ptr, coff);
     GCG_HIP_CHECK(hipGetLastError());
-    tb = tmp_bytes;
-    GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(b_tmp.p, tb, coff, coff, static_cast<int>(nnz_c), st));
+    GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceScan::ExclusiveSum, coff, coff, static_cast<int>(nnz_c), st)));
     hipLaunchKernelGGL((spgemm_expand_kernel<TA, TACC>), dim3(grid_for(nnz_c)), dim3(256), 0, st, nnz_c, p,
                        row_of, a_idx + base, a_val + base, b_ptr, b_idx, b_val, coff, keys, seq, prod);
     GCG_HIP_CHECK(hipGetLastError());
-    tb = tmp_bytes;
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(b_tmp.p, tb, keys, keys2, seq, seq2, static_cast<int>(P), 0, end_bit, st));
+    GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceRadixSort::SortPairs, keys, keys2, seq, seq2, static_cast<int>(P), 0,
+        end_bit, st)));
     hipLaunchKernelGGL(run_flags_kernel, dim3(grid_for(P)), dim3(256), 0, st, P, keys2, flags);
     GCG_HIP_CHECK(hipGetLastError());
     // run starts (positions) and run keys
     hipLaunchKernelGGL(iota_kernel, dim3(grid_for(P)), dim3(256), 0, st, seq, P);  // reuse seq as positions
-    tb = tmp_bytes;
-    GCG_HIP_CHECK(hipcub::DeviceSelect::Flagged(b_tmp.p, tb, seq, flags, starts, cnts, static_cast<int>(P), st));
-    tb = tmp_bytes;
-    GCG_HIP_CHECK(hipcub::DeviceSelect::Flagged(b_tmp.p, tb, keys2, flags, keys, cnts, static_cast<int>(P), st));
+    GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceSelect::Flagged, seq, flags, starts, cnts, static_cast<int>(P), st)));
+    GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceSelect::Flagged, keys2, flags, keys, cnts, static_cast<int>(P), st)));
     int64_t n_runs = 0;
     GCG_HIP_CHECK(hipMemcpyAsync(&n_runs, cnts, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     GCG_HIP_CHECK(hipStreamSynchronize(st));
@@ -843,10 +818,10 @@ gcg_status spgemm_impl(int64_t m, int64_t n, int64_t p, int64_t nnz_a, const int
                        seq2, prod, sums, flags);
     GCG_HIP_CHECK(hipGetLastError());
     // drop exact zeros: compact keys and sums by keep flags
-    tb = tmp_bytes;
-    GCG_HIP_CHECK(hipcub::DeviceSelect::Flagged(b_tmp.p, tb, keys, flags, keys2, cnts, static_cast<int>(n_runs), st));
-    tb = tmp_bytes;
-    GCG_HIP_CHECK(hipcub::DeviceSelect::Flagged(b_tmp.p, tb, sums, flags, prod, cnts + 1, static_cast<int>(n_runs), st));
+    GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceSelect::Flagged, keys, flags, keys2, cnts, static_cast<int>(n_runs),
+        st)));
+    GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceSelect::Flagged, sums, flags, prod, cnts + 1,
+        static_cast<int>(n_runs), st)));
     hipLaunchKernelGGL((spgemm_emit_kernel<TACC>), dim3(grid_for(n_runs)), dim3(256), 0, st, p, keys2,
                        prod, cnts, c_idx + nnz_done, c_val + nnz_done);
     hipLaunchKernelGGL(row_ptr_from_rowkeys_kernel, dim3(grid_for(mc + 1)), dim3(256), 0, st, mc, p, keys2,
@@ -877,20 +852,22 @@ gcg_status gcg_spgemm_products(int64_t m, int64_t nnz_a, const int32_t* a_ptr, c
   *n_products = 0;
   if (nnz_a == 0) return GCG_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  DevBuf cnt, tot, tmp;
-  cnt.s = tot.s = tmp.s = st;
-  size_t tb = 0;
-  int64_t* dummy = nullptr;
-  GCG_HIP_CHECK(hipcub::DeviceReduce::Sum(nullptr, tb, dummy, dummy, static_cast<int>(nnz_a)));
-  GCG_HIP_CHECK(hipMallocAsync(&cnt.p, nnz_a * sizeof(int64_t), st));
-  GCG_HIP_CHECK(hipMallocAsync(&tot.p, sizeof(int64_t), st));
-  GCG_HIP_CHECK(hipMallocAsync(&tmp.p, std::max<size_t>(tb, 16), st));
-  hipLaunchKernelGGL(spgemm_count_kernel, dim3(grid_for(nnz_a)), dim3(256), 0, st, nnz_a, a_idx, b_ptr,
-                     static_cast<int64_t*>(cnt.p));
+  // the per-nonzero counts, their total, hipcub's temporary: one allocation, carved
+  int64_t *cnt = nullptr, *tot = nullptr;
+  Tmp tmp;
+  TmpSize ts;
+  ts.add(GCG_CUB(DeviceReduce::Sum, cnt, tot, static_cast<int>(nnz_a)));
+  if (gcg_status rc = ts.status("gcg_spgemm_products")) return rc;
+  DevMem mem;
+  GCG_HIP_CHECK(alloc_carved(mem, st, [&](Carver& cv) {
+    cnt = cv.take<int64_t>(nnz_a);
+    tot = cv.take<int64_t>(1);
+    tmp = {cv.take<char>(ts.bytes), ts.bytes};
+  }));
+  hipLaunchKernelGGL(spgemm_count_kernel, dim3(grid_for(nnz_a)), dim3(256), 0, st, nnz_a, a_idx, b_ptr, cnt);
   GCG_HIP_CHECK(hipGetLastError());
-  GCG_HIP_CHECK(hipcub::DeviceReduce::Sum(tmp.p, tb, static_cast<int64_t*>(cnt.p), static_cast<int64_t*>(tot.p),
-                                          static_cast<int>(nnz_a), st));
-  GCG_HIP_CHECK(hipMemcpyAsync(n_products, tot.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  GCG_HIP_CHECK(tmp.run(GCG_CUB(DeviceReduce::Sum, cnt, tot, static_cast<int>(nnz_a), st)));
+  GCG_HIP_CHECK(hipMemcpyAsync(n_products, tot, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   GCG_HIP_CHECK(hipStreamSynchronize(st));
   return GCG_OK;
 }

@@ -8,7 +8,7 @@
 
 #include <cmath>
 
-#include "common.h"
+#include "scratch.h"
 
 using namespace gcg;
 
@@ -17,13 +17,6 @@ namespace {
 // A dropped token (id outside [0, V)): every sorted bit set, and the bit above the document's
 // bits, which no kept key has, so the dropped tokens sort behind every document.
 constexpr uint64_t kDropped = ~uint64_t{0};
-
-// Bits that hold every value in [0, max_value].
-int bits_of(uint64_t max_value) {
-  int b = 1;
-  while (b < 63 && (uint64_t{1} << b) <= max_value) ++b;
-  return b;
-}
 
 // ---- count --------------------------------------------------------------------------------
 
@@ -129,49 +122,51 @@ __global__ void tfidf_advance_kernel(const uint64_t* __restrict__ uniq,
   else *nnz_dev = base + n;
 }
 
-struct CountLayout {
+// The scratch of a count, in the order of the take calls. The sorted keys are dead once the
+// runs are encoded, and the term-ordered document frequency then sorts the entries' columns
+// in their region: sorted keys | columns, sorted columns.
+struct CountSpace {
   int vbits, end_bit, cbits;
-  size_t off_a, off_b, off_len, off_term, off_tlen, off_runs, off_tmp, tmp_bytes, total;
+  uint64_t *key_a, *key_b;  // keys, then the unique keys | sorted keys
+  int32_t *cols, *cols_sorted;
+  int32_t *run_len, *term, *term_len, *num_runs;  // (terms and lengths of the column runs)
+  Tmp tmp;
+  size_t total;
 };
 
-// Workspace: [keys | unique keys][sorted keys | columns, sorted columns][run lengths]
-// [terms of the column runs][their lengths][run counts][hipcub temporary].
-gcg_status count_layout(const char* fn, int64_t n_docs, int64_t n_tokens, int64_t V, bool sized,
-                        CountLayout* L) {
+// The arguments, then the fixed arrays (no HIP device), then with `sized` the hipcub temporary:
+// rocPRIM sizes it for the device's architecture, so that half needs a HIP device.
+gcg_status count_space(const char* fn, int64_t n_docs, int64_t n_tokens, int64_t V, void* workspace,
+                       bool sized, CountSpace* s) {
   if (n_docs < 0 || n_docs >= INT32_MAX || n_tokens < 0 || n_tokens >= INT32_MAX || V < 1 ||
       V >= INT32_MAX)
     return fail(GCG_ERR_INVALID_ARG, "%s: bad sizes n_docs=%lld n_tokens=%lld n_terms=%lld "
                 "(each below 2^31 - 1, n_terms >= 1)", fn, static_cast<long long>(n_docs),
                 static_cast<long long>(n_tokens), static_cast<long long>(V));
-  L->vbits = bits_of(static_cast<uint64_t>(V - 1));
-  L->end_bit = L->vbits + bits_of(static_cast<uint64_t>(std::max<int64_t>(n_docs, 1) - 1)) + 1;
-  L->cbits = bits_of(static_cast<uint64_t>(V));
+  s->vbits = bits_to_hold(static_cast<uint64_t>(V - 1));
+  s->end_bit = s->vbits + bits_to_hold(static_cast<uint64_t>(std::max<int64_t>(n_docs, 1) - 1)) + 1;
+  s->cbits = bits_to_hold(static_cast<uint64_t>(V));
+  // take_exact throughout: a chunk without tokens has empty arrays
   const size_t n8 = align_up(static_cast<size_t>(n_tokens) * 8, 256);
   const size_t n4 = align_up(static_cast<size_t>(n_tokens) * 4, 256);
-  size_t o = 0;
-  L->off_a = o;    o += n8;
-  L->off_b = o;    o += std::max(n8, 2 * n4);
-  L->off_len = o;  o += n4;
-  L->off_term = o; o += n4;
-  L->off_tlen = o; o += n4;
-  L->off_runs = o; o += 256;
-  L->off_tmp = o;
-  L->tmp_bytes = 0;
-  L->total = o;
-  if (!sized) return GCG_OK;
-  // rocPRIM sizes its temporary for the device's architecture: this half needs a HIP device
-  size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0;
+  Carver cv(workspace);
+  s->key_a = cv.take_exact<uint64_t>(n_tokens);
+  s->key_b = cv.take_bytes<uint64_t>(std::max(n8, 2 * n4));
+  s->cols = reinterpret_cast<int32_t*>(s->key_b);
+  s->cols_sorted = s->cols ? s->cols + n4 / 4 : nullptr;
+  s->run_len = cv.take_exact<int32_t>(n_tokens);
+  s->term = cv.take_exact<int32_t>(n_tokens);
+  s->term_len = cv.take_exact<int32_t>(n_tokens);
+  s->num_runs = cv.take_bytes<int32_t>(256);  // [0] the keys' runs, [1] the columns'
   const int n = static_cast<int>(std::max<int64_t>(n_tokens, 1));
-  uint64_t* k = nullptr;
-  int32_t* c = nullptr;
-  hipError_t e = hipcub::DeviceRadixSort::SortKeys(nullptr, t1, k, k, n, 0, L->end_bit);
-  if (e == hipSuccess) e = hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, k, k, c, c, n);
-  if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortKeys(nullptr, t3, c, c, n, 0, L->cbits);
-  if (e == hipSuccess) e = hipcub::DeviceRunLengthEncode::Encode(nullptr, t4, c, c, c, c, n);
-  if (e != hipSuccess) return fail(GCG_ERR_HIP, "%s: hipcub sizing: %s", fn, hipGetErrorString(e));
-  L->tmp_bytes = std::max(std::max(t1, t2), std::max(t3, t4));
-  L->total = L->off_tmp + align_up(L->tmp_bytes, 256);
-  return GCG_OK;
+  TmpSize ts;
+  if (sized) {
+    ts.add(GCG_CUB(DeviceRadixSort::SortKeys, s->key_a, s->key_b, n, 0, s->end_bit));
+    ts.add(GCG_CUB(DeviceRunLengthEncode::Encode, s->key_b, s->key_a, s->run_len, s->num_runs, n));
+    ts.add(GCG_CUB(DeviceRadixSort::SortKeys, s->cols, s->cols_sorted, n, 0, s->cbits));
+    ts.add(GCG_CUB(DeviceRunLengthEncode::Encode, s->cols_sorted, s->term, s->term_len, s->num_runs, n));
+  }
+  return ts.take_exact(fn, cv, &s->tmp, &s->total);
 }
 
 // ---- select -------------------------------------------------------------------------------
@@ -313,6 +308,43 @@ gcg_status compact_sizes(const char* fn, int64_t n_rows, int64_t V, int64_t nnz)
   return GCG_OK;
 }
 
+// The scratch of a selection: the keep flags, their exclusive sum, hipcub's temporary.
+struct SelectSpace {
+  int32_t *keep, *pos;
+  Tmp tmp;
+  size_t total;
+};
+
+gcg_status select_space(const char* fn, int64_t n_terms, void* workspace, bool sized,
+                        SelectSpace* s) {
+  if (n_terms < 1 || n_terms >= INT32_MAX)
+    return fail(GCG_ERR_INVALID_ARG, "%s: bad n_terms=%lld", fn, static_cast<long long>(n_terms));
+  Carver cv(workspace);
+  s->keep = cv.take_exact<int32_t>(n_terms);
+  s->pos = cv.take_exact<int32_t>(n_terms);
+  TmpSize ts;
+  if (sized) {
+    ts.add(GCG_CUB(DeviceScan::ExclusiveSum, s->keep, s->pos, static_cast<int>(n_terms)));
+  }
+  return ts.take_exact(fn, cv, &s->tmp, &s->total);
+}
+
+// The scratch of a compaction's sizing call: the kept entries per row (n_rows + 1), hipcub's
+// temporary for their exclusive sum into out_indptr. The callers have validated n_rows.
+struct CompactSpace {
+  int32_t* len;
+  Tmp tmp;
+  size_t total;
+};
+
+gcg_status compact_space(const char* fn, int64_t n_rows, void* workspace, CompactSpace* s) {
+  Carver cv(workspace);
+  s->len = cv.take_exact<int32_t>(n_rows + 1);
+  TmpSize ts;
+  ts.add(GCG_CUB(DeviceScan::ExclusiveSum, s->len, s->len, static_cast<int>(n_rows + 1)));
+  return ts.take_exact(fn, cv, &s->tmp, &s->total);
+}
+
 }  // namespace
 
 extern "C" {
@@ -322,9 +354,9 @@ gcg_status gcg_tfidf_count_workspace_bytes(int64_t n_docs, int64_t n_tokens, int
   const char* fn = "gcg_tfidf_count_workspace_bytes";
   if (bytes == nullptr) return fail(GCG_ERR_INVALID_ARG, "%s: NULL bytes", fn);
   *bytes = 0;
-  CountLayout L;
-  if (const gcg_status st = count_layout(fn, n_docs, n_tokens, n_terms, true, &L)) return st;
-  *bytes = L.total;
+  CountSpace s;
+  if (const gcg_status st = count_space(fn, n_docs, n_tokens, n_terms, nullptr, true, &s)) return st;
+  *bytes = s.total;
   return GCG_OK;
 }
 
@@ -334,8 +366,8 @@ gcg_status gcg_tfidf_count(int64_t n_docs, int64_t n_terms, int64_t n_tokens,
                            int64_t* nnz_dev, int64_t* df, int32_t df_mode, int32_t* status_dev,
                            void* workspace, size_t workspace_bytes, gcg_stream_t stream) {
   const char* fn = "gcg_tfidf_count";
-  CountLayout L;
-  if (const gcg_status st = count_layout(fn, n_docs, n_tokens, n_terms, false, &L)) return st;
+  CountSpace s;
+  if (const gcg_status st = count_space(fn, n_docs, n_tokens, n_terms, nullptr, false, &s)) return st;
   const bool sizing = indptr == nullptr && indices == nullptr && counts == nullptr;
   if (!sizing && (indptr == nullptr || indices == nullptr || counts == nullptr))
     return fail(GCG_ERR_INVALID_ARG, "%s: indptr, indices and counts are all NULL (sizing) or "
@@ -351,60 +383,47 @@ gcg_status gcg_tfidf_count(int64_t n_docs, int64_t n_terms, int64_t n_tokens,
       !aligned(rank, 4) || !aligned(indptr, 4) || !aligned(indices, 4) || !aligned(counts, 4) ||
       !aligned(status_dev, 4) || !aligned(workspace, 8))
     return fail(GCG_ERR_MISALIGNED, "%s: a buffer is not aligned to its element size", fn);
-  if (const gcg_status st = count_layout(fn, n_docs, n_tokens, n_terms, true, &L)) return st;
-  if (workspace_bytes < L.total)
-    return fail(GCG_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, L.total);
+  if (const gcg_status st = count_space(fn, n_docs, n_tokens, n_terms, workspace, true, &s))
+    return st;
+  if (const gcg_status st = check_workspace(fn, workspace, workspace_bytes, s.total, 8)) return st;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(workspace);
-  uint64_t* key_a = reinterpret_cast<uint64_t*>(w + L.off_a);
-  uint64_t* key_b = reinterpret_cast<uint64_t*>(w + L.off_b);
-  int32_t* run_len = reinterpret_cast<int32_t*>(w + L.off_len);
-  int32_t* num_runs = reinterpret_cast<int32_t*>(w + L.off_runs);
-  void* tmp = w + L.off_tmp;
   const int n = static_cast<int>(n_tokens);
   // a sizing call only moves nnz_dev on: no capacity to exceed, nothing else written
   const int64_t cap = sizing ? INT64_MAX : capacity;
-  GCG_HIP_CHECK(hipMemsetAsync(num_runs, 0, 256, st));
+  GCG_HIP_CHECK(hipMemsetAsync(s.num_runs, 0, 256, st));
   if (n_tokens > 0) {
-    GCG_HIP_CHECK(hipMemsetAsync(key_a, 0xff, static_cast<size_t>(n_tokens) * 8, st));
+    GCG_HIP_CHECK(hipMemsetAsync(s.key_a, 0xff, static_cast<size_t>(n_tokens) * 8, st));
     hipLaunchKernelGGL(tfidf_keys_kernel, dim3(wave_grid(n_docs)), dim3(kBlock), 0, st, n_docs,
-                       n_terms, L.vbits, doc_ptr, tokens, n_tokens, rank, key_a);
+                       n_terms, s.vbits, doc_ptr, tokens, n_tokens, rank, s.key_a);
     GCG_HIP_CHECK(hipGetLastError());
-    size_t t = L.tmp_bytes;
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(tmp, t, key_a, key_b, n, 0, L.end_bit, st));
-    t = L.tmp_bytes;
-    GCG_HIP_CHECK(hipcub::DeviceRunLengthEncode::Encode(tmp, t, key_b, key_a, run_len, num_runs, n,
-                                                        st));
+    GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceRadixSort::SortKeys, s.key_a, s.key_b, n, 0, s.end_bit, st)));
+    GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceRunLengthEncode::Encode, s.key_b, s.key_a, s.run_len, s.num_runs, n,
+        st)));
   }
+  const bool ordered = !sizing && df != nullptr && df_mode == 1 && n_tokens > 0;
   if (!sizing) {
-    const bool ordered = df != nullptr && df_mode == 1 && n_tokens > 0;
-    int32_t* cols = ordered ? reinterpret_cast<int32_t*>(w + L.off_b) : nullptr;
+    // the sorted keys are dead: with the ordered df the entries' columns take their region
     hipLaunchKernelGGL(tfidf_decode_kernel, dim3(grid_for(std::max<int64_t>(n_tokens, 1))),
-                       dim3(256), 0, st, n_tokens, n_terms, L.vbits, key_a, run_len, num_runs,
-                       nnz_dev, cap, indices, counts, reinterpret_cast<unsigned long long*>(df),
-                       cols);
+                       dim3(256), 0, st, n_tokens, n_terms, s.vbits, s.key_a, s.run_len,
+                       s.num_runs, nnz_dev, cap, indices, counts,
+                       reinterpret_cast<unsigned long long*>(df), ordered ? s.cols : nullptr);
     GCG_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(tfidf_indptr_kernel, dim3(grid_for(n_docs + 1)), dim3(256), 0, st, n_docs,
-                       L.vbits, key_a, num_runs, nnz_dev, cap, indptr);
+                       s.vbits, s.key_a, s.num_runs, nnz_dev, cap, indptr);
     GCG_HIP_CHECK(hipGetLastError());
   }
-  hipLaunchKernelGGL(tfidf_advance_kernel, dim3(1), dim3(kWave), 0, st, key_a, num_runs, cap,
+  hipLaunchKernelGGL(tfidf_advance_kernel, dim3(1), dim3(kWave), 0, st, s.key_a, s.num_runs, cap,
                      nnz_dev, status_dev);
   GCG_HIP_CHECK(hipGetLastError());
-  if (!sizing && df != nullptr && df_mode == 1 && n_tokens > 0) {
+  if (ordered) {
     // The columns were written only where the chunk fitted; a chunk that did not fit has set
     // status_dev, and the caller drops everything, df included.
-    int32_t* cols = reinterpret_cast<int32_t*>(w + L.off_b);
-    int32_t* cols_sorted = cols + align_up(static_cast<size_t>(n_tokens) * 4, 256) / 4;
-    int32_t* term = reinterpret_cast<int32_t*>(w + L.off_term);
-    int32_t* term_len = reinterpret_cast<int32_t*>(w + L.off_tlen);
-    size_t t = L.tmp_bytes;
-    GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(tmp, t, cols, cols_sorted, n, 0, L.cbits, st));
-    t = L.tmp_bytes;
-    GCG_HIP_CHECK(hipcub::DeviceRunLengthEncode::Encode(tmp, t, cols_sorted, term, term_len,
-                                                        num_runs + 1, n, st));
+    GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceRadixSort::SortKeys, s.cols, s.cols_sorted, n, 0, s.cbits, st)));
+    GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceRunLengthEncode::Encode, s.cols_sorted, s.term, s.term_len,
+        s.num_runs + 1, n, st)));
     hipLaunchKernelGGL(tfidf_df_runs_kernel, dim3(grid_for(n_tokens)), dim3(256), 0, st, n_terms,
-                       term, term_len, num_runs + 1, reinterpret_cast<unsigned long long*>(df));
+                       s.term, s.term_len, s.num_runs + 1,
+                       reinterpret_cast<unsigned long long*>(df));
     GCG_HIP_CHECK(hipGetLastError());
   }
   return GCG_OK;
@@ -414,13 +433,9 @@ gcg_status gcg_tfidf_select_workspace_bytes(int64_t n_terms, size_t* bytes) {
   const char* fn = "gcg_tfidf_select_workspace_bytes";
   if (bytes == nullptr) return fail(GCG_ERR_INVALID_ARG, "%s: NULL bytes", fn);
   *bytes = 0;
-  if (n_terms < 1 || n_terms >= INT32_MAX)
-    return fail(GCG_ERR_INVALID_ARG, "%s: bad n_terms=%lld", fn, static_cast<long long>(n_terms));
-  size_t t = 0;
-  int32_t* p = nullptr;
-  const hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, t, p, p, static_cast<int>(n_terms));
-  if (e != hipSuccess) return fail(GCG_ERR_HIP, "%s: hipcub sizing: %s", fn, hipGetErrorString(e));
-  *bytes = 2 * align_up(static_cast<size_t>(n_terms) * 4, 256) + align_up(t, 256);
+  SelectSpace s;
+  if (const gcg_status st = select_space(fn, n_terms, nullptr, true, &s)) return st;
+  *bytes = s.total;
   return GCG_OK;
 }
 
@@ -428,31 +443,23 @@ gcg_status gcg_tfidf_select(int64_t n_terms, const int64_t* df, int64_t lo, int6
                             int32_t* new_id, int64_t* kept_df, int64_t* n_kept_dev,
                             void* workspace, size_t workspace_bytes, gcg_stream_t stream) {
   const char* fn = "gcg_tfidf_select";
-  if (n_terms < 1 || n_terms >= INT32_MAX)
-    return fail(GCG_ERR_INVALID_ARG, "%s: bad n_terms=%lld", fn, static_cast<long long>(n_terms));
+  SelectSpace s;
+  if (const gcg_status st = select_space(fn, n_terms, nullptr, false, &s)) return st;
   if (df == nullptr || new_id == nullptr || kept_df == nullptr || n_kept_dev == nullptr ||
       workspace == nullptr)
     return fail(GCG_ERR_INVALID_ARG, "%s: NULL df, new_id, kept_df, n_kept_dev or workspace", fn);
   if (!aligned(df, 8) || !aligned(kept_df, 8) || !aligned(n_kept_dev, 8) || !aligned(new_id, 4) ||
       !aligned(workspace, 8))
     return fail(GCG_ERR_MISALIGNED, "%s: a buffer is not aligned to its element size", fn);
-  size_t need = 0;
-  if (const gcg_status st = gcg_tfidf_select_workspace_bytes(n_terms, &need)) return st;
-  if (workspace_bytes < need)
-    return fail(GCG_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, need);
+  if (const gcg_status st = select_space(fn, n_terms, workspace, true, &s)) return st;
+  if (const gcg_status st = check_workspace(fn, workspace, workspace_bytes, s.total, 8)) return st;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t n4 = align_up(static_cast<size_t>(n_terms) * 4, 256);
-  char* w = static_cast<char*>(workspace);
-  int32_t* keep = reinterpret_cast<int32_t*>(w);
-  int32_t* pos = reinterpret_cast<int32_t*>(w + n4);
-  size_t t = need - 2 * n4;
   hipLaunchKernelGGL(tfidf_keep_kernel, dim3(grid_for(n_terms)), dim3(256), 0, st, n_terms, df, lo,
-                     hi, keep);
+                     hi, s.keep);
   GCG_HIP_CHECK(hipGetLastError());
-  GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(w + 2 * n4, t, keep, pos,
-                                                 static_cast<int>(n_terms), st));
+  GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceScan::ExclusiveSum, s.keep, s.pos, static_cast<int>(n_terms), st)));
   hipLaunchKernelGGL(tfidf_renumber_kernel, dim3(grid_for(n_terms)), dim3(256), 0, st, n_terms, df,
-                     keep, pos, new_id, kept_df, n_kept_dev);
+                     s.keep, s.pos, new_id, kept_df, n_kept_dev);
   GCG_HIP_CHECK(hipGetLastError());
   return GCG_OK;
 }
@@ -479,11 +486,9 @@ gcg_status gcg_tfidf_compact_workspace_bytes(int64_t n_rows, size_t* bytes) {
   *bytes = 0;
   if (n_rows < 0 || n_rows >= INT32_MAX)
     return fail(GCG_ERR_INVALID_ARG, "%s: bad n_rows=%lld", fn, static_cast<long long>(n_rows));
-  size_t t = 0;
-  int32_t* p = nullptr;
-  const hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, t, p, p, static_cast<int>(n_rows + 1));
-  if (e != hipSuccess) return fail(GCG_ERR_HIP, "%s: hipcub sizing: %s", fn, hipGetErrorString(e));
-  *bytes = align_up(static_cast<size_t>(n_rows + 1) * 4, 256) + align_up(t, 256);
+  CompactSpace s;
+  if (const gcg_status st = compact_space(fn, n_rows, nullptr, &s)) return st;
+  *bytes = s.total;
   return GCG_OK;
 }
 
@@ -509,19 +514,14 @@ gcg_status gcg_tfidf_compact(int64_t n_rows, int64_t n_terms, int64_t nnz, const
     return fail(GCG_ERR_MISALIGNED, "%s: a buffer is not aligned to its element size", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (sizing) {  // out_indptr alone: out_indptr[n_rows] is the entry count the second call needs
-    size_t need = 0;
-    if (const gcg_status s = gcg_tfidf_compact_workspace_bytes(n_rows, &need)) return s;
-    if (workspace_bytes < need)
-      return fail(GCG_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, need);
-    const size_t n4 = align_up(static_cast<size_t>(n_rows + 1) * 4, 256);
-    char* w = static_cast<char*>(workspace);
-    int32_t* len = reinterpret_cast<int32_t*>(w);
+    CompactSpace s;
+    if (const gcg_status rc = compact_space(fn, n_rows, workspace, &s)) return rc;
+    if (const gcg_status rc = check_workspace(fn, workspace, workspace_bytes, s.total, 8)) return rc;
     hipLaunchKernelGGL(tfidf_row_kept_kernel, dim3(wave_grid(n_rows + 1)), dim3(kBlock), 0, st,
-                       n_rows, n_terms, nnz, indptr, indices, new_id, len);
+                       n_rows, n_terms, nnz, indptr, indices, new_id, s.len);
     GCG_HIP_CHECK(hipGetLastError());
-    size_t t = need - n4;
-    GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(w + n4, t, len, out_indptr,
-                                                   static_cast<int>(n_rows + 1), st));
+    GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceScan::ExclusiveSum, s.len, out_indptr, static_cast<int>(n_rows + 1),
+        st)));
     return GCG_OK;
   }
   if (n_rows == 0) return GCG_OK;

@@ -15,7 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include "common.h"
+#include "scratch.h"
 
 using namespace gcg;
 
@@ -318,72 +318,90 @@ int tile_grid(int64_t n_tiles) {
   return static_cast<int>(std::min<int64_t>(std::max<int64_t>(n_tiles, 1), 1 << 16));
 }
 
-gcg_status mark_sizes(const char* fn, int64_t n_bytes, size_t* scan_tmp) {
+// Every space below: the arguments, then the fixed arrays in the order of the take calls (no HIP
+// device), then with `sized` the hipcub temporary -- rocPRIM sizes it for the device's
+// architecture, so that half needs a HIP device. take_exact throughout: no tokens, empty arrays.
+
+// The scratch of the marking: the tiles' packed counts (and a total), hipcub's temporary.
+struct MarkSpace {
+  u64* cnt;
+  Tmp tmp;
+  size_t total;
+};
+
+gcg_status mark_space(const char* fn, int64_t n_bytes, void* workspace, bool sized, MarkSpace* s) {
   // a token takes at least three bytes with its separator: below 2^33 bytes the token count
   // fits the low half of a tile's packed count
   if (n_bytes < 0 || n_bytes > (int64_t{1} << 33))
     return fail(GCG_ERR_INVALID_ARG, "%s: bad n_bytes=%lld (at most 2^33)", fn,
                 static_cast<long long>(n_bytes));
-  u64* p = nullptr;
-  const hipError_t e = hipcub::DeviceScan::ExclusiveSum(
-      nullptr, *scan_tmp, p, p, static_cast<int>(tiles_of(n_bytes) + 1));
-  if (e != hipSuccess) return fail(GCG_ERR_HIP, "%s: hipcub sizing: %s", fn, hipGetErrorString(e));
-  return GCG_OK;
+  Carver cv(workspace);
+  s->cnt = cv.take_exact<u64>(tiles_of(n_bytes) + 1);
+  TmpSize ts;
+  if (sized) {
+    ts.add(GCG_CUB(DeviceScan::ExclusiveSum, s->cnt, s->cnt, static_cast<int>(tiles_of(n_bytes) + 1)));
+  }
+  return ts.take_exact(fn, cv, &s->tmp, &s->total);
 }
 
-struct TermsLayout {
-  size_t off_key_a, off_key_b, off_start, off_idx_a, off_idx_b, off_len, off_head, off_rep,
-      off_first, off_fid, off_tmp, tmp_bytes, total;
+// The scratch of the term dictionary.
+struct TermsSpace {
+  u64 *key_a, *key_b;        // hashes, sorted hashes
+  int64_t* tok_start;
+  int32_t *idx_a, *idx_b;    // token indices, sorted indices
+  int32_t *tok_len, *head, *rep_tok, *is_first, *first_id;
+  Tmp tmp;
+  size_t total;
 };
 
-// Workspace: [hashes][sorted hashes][token starts][token indices][sorted indices][token lengths]
-// [run heads][representatives][first flags][first-appearance numbers][hipcub temporary].
-gcg_status terms_layout(const char* fn, int64_t n_tokens, int hash_bits, bool sized, TermsLayout* L) {
+gcg_status terms_space(const char* fn, int64_t n_tokens, int hash_bits, void* workspace, bool sized,
+                       TermsSpace* s) {
   if (n_tokens < 0 || n_tokens >= INT32_MAX || hash_bits < 1 || hash_bits > 64)
     return fail(GCG_ERR_INVALID_ARG, "%s: bad n_tokens=%lld (below 2^31 - 1) or hash_bits=%d "
                 "(1 .. 64)", fn, static_cast<long long>(n_tokens), hash_bits);
-  const size_t n8 = align_up(static_cast<size_t>(n_tokens) * 8, 256);
-  const size_t n4 = align_up(static_cast<size_t>(n_tokens) * 4, 256);
-  size_t o = 0;
-  L->off_key_a = o; o += n8;
-  L->off_key_b = o; o += n8;
-  L->off_start = o; o += n8;
-  L->off_idx_a = o; o += n4;
-  L->off_idx_b = o; o += n4;
-  L->off_len = o;   o += n4;
-  L->off_head = o;  o += n4;
-  L->off_rep = o;   o += n4;
-  L->off_first = o; o += n4;
-  L->off_fid = o;   o += n4;
-  L->off_tmp = o;
-  L->tmp_bytes = 0;
-  L->total = o;
-  if (!sized) return GCG_OK;
-  size_t t1 = 0, t2 = 0, t3 = 0;
+  Carver cv(workspace);
+  s->key_a = cv.take_exact<u64>(n_tokens);
+  s->key_b = cv.take_exact<u64>(n_tokens);
+  s->tok_start = cv.take_exact<int64_t>(n_tokens);
+  s->idx_a = cv.take_exact<int32_t>(n_tokens);
+  s->idx_b = cv.take_exact<int32_t>(n_tokens);
+  s->tok_len = cv.take_exact<int32_t>(n_tokens);
+  s->head = cv.take_exact<int32_t>(n_tokens);
+  s->rep_tok = cv.take_exact<int32_t>(n_tokens);
+  s->is_first = cv.take_exact<int32_t>(n_tokens);
+  s->first_id = cv.take_exact<int32_t>(n_tokens);
   const int n = static_cast<int>(std::max<int64_t>(n_tokens, 1));
-  u64* k = nullptr;
-  int32_t* c = nullptr;
-  hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, t1, k, k, c, c, n, 0, hash_bits);
-  if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveScan(nullptr, t2, c, c, hipcub::Max(), n);
-  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, t3, c, c, n);
-  if (e != hipSuccess) return fail(GCG_ERR_HIP, "%s: hipcub sizing: %s", fn, hipGetErrorString(e));
-  L->tmp_bytes = std::max(t1, std::max(t2, t3));
-  L->total = L->off_tmp + align_up(L->tmp_bytes, 256);
-  return GCG_OK;
+  TmpSize ts;
+  if (sized) {
+    ts.add(GCG_CUB(DeviceRadixSort::SortPairs, s->key_a, s->key_b, s->idx_a, s->idx_b, n, 0, hash_bits));
+    ts.add(GCG_CUB(DeviceScan::InclusiveScan, s->idx_a, s->head, hipcub::Max(), n));
+    ts.add(GCG_CUB(DeviceScan::ExclusiveSum, s->is_first, s->first_id, n));
+  }
+  return ts.take_exact(fn, cv, &s->tmp, &s->total);
 }
 
-gcg_status remap_sizes(const char* fn, int64_t n_tokens, int64_t n_docs, int64_t n_terms,
-                       size_t* scan_tmp) {
+// The scratch of the remap: the keep flags (n_tokens + 1), their exclusive sum, hipcub's.
+struct RemapSpace {
+  int32_t *keep, *pos;
+  Tmp tmp;
+  size_t total;
+};
+
+gcg_status remap_space(const char* fn, int64_t n_tokens, int64_t n_docs, int64_t n_terms,
+                       void* workspace, bool sized, RemapSpace* s) {
   if (n_tokens < 0 || n_tokens >= INT32_MAX - 1 || n_docs < 0 || n_docs >= INT32_MAX ||
       n_terms < 0 || n_terms > n_tokens)
     return fail(GCG_ERR_INVALID_ARG, "%s: bad sizes n_tokens=%lld n_docs=%lld n_terms=%lld", fn,
                 static_cast<long long>(n_tokens), static_cast<long long>(n_docs),
                 static_cast<long long>(n_terms));
-  int32_t* p = nullptr;
-  const hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, *scan_tmp, p, p,
-                                                        static_cast<int>(n_tokens + 1));
-  if (e != hipSuccess) return fail(GCG_ERR_HIP, "%s: hipcub sizing: %s", fn, hipGetErrorString(e));
-  return GCG_OK;
+  Carver cv(workspace);
+  s->keep = cv.take_exact<int32_t>(n_tokens + 1);
+  s->pos = cv.take_exact<int32_t>(n_tokens + 1);
+  TmpSize ts;
+  if (sized) {
+    ts.add(GCG_CUB(DeviceScan::ExclusiveSum, s->keep, s->pos, static_cast<int>(n_tokens + 1)));
+  }
+  return ts.take_exact(fn, cv, &s->tmp, &s->total);
 }
 
 }  // namespace
@@ -396,9 +414,9 @@ gcg_status gcg_tokenize_mark_workspace_bytes(int64_t n_bytes, size_t* bytes) {
   const char* fn = "gcg_tokenize_mark_workspace_bytes";
   if (bytes == nullptr) return fail(GCG_ERR_INVALID_ARG, "%s: NULL bytes", fn);
   *bytes = 0;
-  size_t t = 0;
-  if (const gcg_status st = mark_sizes(fn, n_bytes, &t)) return st;
-  *bytes = align_up(static_cast<size_t>(tiles_of(n_bytes) + 1) * 8, 256) + align_up(t, 256);
+  MarkSpace s;
+  if (const gcg_status st = mark_space(fn, n_bytes, nullptr, true, &s)) return st;
+  *bytes = s.total;
   return GCG_OK;
 }
 
@@ -407,10 +425,8 @@ gcg_status gcg_tokenize_mark(int64_t n_bytes, const uint8_t* text, const uint32_
                              int64_t* totals_dev, void* workspace, size_t workspace_bytes,
                              gcg_stream_t stream) {
   const char* fn = "gcg_tokenize_mark";
-  size_t need = 0, t = 0;
-  if (n_bytes < 0 || n_bytes > (int64_t{1} << 33))
-    return fail(GCG_ERR_INVALID_ARG, "%s: bad n_bytes=%lld (at most 2^33)", fn,
-                static_cast<long long>(n_bytes));
+  MarkSpace s;
+  if (const gcg_status st = mark_space(fn, n_bytes, nullptr, false, &s)) return st;
   if (word_table == nullptr || tile_base == nullptr || totals_dev == nullptr || workspace == nullptr ||
       (n_bytes > 0 && (text == nullptr || flags == nullptr)))
     return fail(GCG_ERR_INVALID_ARG, "%s: NULL text, word_table, flags, tile_base, totals_dev or "
@@ -419,24 +435,19 @@ gcg_status gcg_tokenize_mark(int64_t n_bytes, const uint8_t* text, const uint32_
       !aligned(tile_base, 8) || !aligned(totals_dev, 8) || !aligned(workspace, 8))
     return fail(GCG_ERR_MISALIGNED, "%s: text and flags must be 16-byte aligned, the other "
                 "buffers to their element size", fn);
-  // rocPRIM sizes its temporary for the device's architecture: from here on a HIP device
-  if (const gcg_status st = gcg_tokenize_mark_workspace_bytes(n_bytes, &need)) return st;
-  if (const gcg_status st = mark_sizes(fn, n_bytes, &t)) return st;
-  if (workspace_bytes < need)
-    return fail(GCG_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, need);
+  // from here on a HIP device
+  if (const gcg_status st = mark_space(fn, n_bytes, workspace, true, &s)) return st;
+  if (const gcg_status st = check_workspace(fn, workspace, workspace_bytes, s.total, 8)) return st;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t n_tiles = tiles_of(n_bytes);
-  char* w = static_cast<char*>(workspace);
-  u64* cnt = reinterpret_cast<u64*>(w);
-  void* tmp = w + align_up(static_cast<size_t>(n_tiles + 1) * 8, 256);
-  GCG_HIP_CHECK(hipMemsetAsync(cnt + n_tiles, 0, 8, st));
+  GCG_HIP_CHECK(hipMemsetAsync(s.cnt + n_tiles, 0, 8, st));
   if (n_tiles > 0) {
     hipLaunchKernelGGL(tokenize_mark_kernel, dim3(tile_grid(n_tiles)), dim3(kThreads), 0, st,
-                       n_bytes, text, word_table, lookbehind != 0, flags, cnt, n_tiles);
+                       n_bytes, text, word_table, lookbehind != 0, flags, s.cnt, n_tiles);
     GCG_HIP_CHECK(hipGetLastError());
   }
-  GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, t, cnt, reinterpret_cast<u64*>(tile_base),
-                                                 static_cast<int>(n_tiles + 1), st));
+  GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceScan::ExclusiveSum, s.cnt, reinterpret_cast<u64*>(tile_base),
+      static_cast<int>(n_tiles + 1), st)));
   hipLaunchKernelGGL(tokenize_totals_kernel, dim3(1), dim3(kWave), 0, st,
                      reinterpret_cast<const u64*>(tile_base), n_tiles, totals_dev);
   GCG_HIP_CHECK(hipGetLastError());
@@ -447,9 +458,9 @@ gcg_status gcg_tokenize_terms_workspace_bytes(int64_t n_tokens, int32_t hash_bit
   const char* fn = "gcg_tokenize_terms_workspace_bytes";
   if (bytes == nullptr) return fail(GCG_ERR_INVALID_ARG, "%s: NULL bytes", fn);
   *bytes = 0;
-  TermsLayout L;
-  if (const gcg_status st = terms_layout(fn, n_tokens, hash_bits, true, &L)) return st;
-  *bytes = L.total;
+  TermsSpace s;
+  if (const gcg_status st = terms_space(fn, n_tokens, hash_bits, nullptr, true, &s)) return st;
+  *bytes = s.total;
   return GCG_OK;
 }
 
@@ -460,8 +471,8 @@ gcg_status gcg_tokenize_terms(int64_t n_bytes, const uint8_t* text, const uint8_
                               int64_t* result_dev, void* workspace, size_t workspace_bytes,
                               gcg_stream_t stream) {
   const char* fn = "gcg_tokenize_terms";
-  TermsLayout L;
-  if (const gcg_status st = terms_layout(fn, n_tokens, hash_bits, false, &L)) return st;
+  TermsSpace s;
+  if (const gcg_status st = terms_space(fn, n_tokens, hash_bits, nullptr, false, &s)) return st;
   if (n_bytes < 0 || n_bytes > (int64_t{1} << 33) || n_docs < 1 || n_docs >= INT32_MAX)
     return fail(GCG_ERR_INVALID_ARG, "%s: bad sizes n_bytes=%lld (at most 2^33) n_docs=%lld (at "
                 "least one document)", fn, static_cast<long long>(n_bytes),
@@ -480,59 +491,44 @@ gcg_status gcg_tokenize_terms(int64_t n_bytes, const uint8_t* text, const uint8_
       !aligned(result_dev, 8) || !aligned(workspace, 8))
     return fail(GCG_ERR_MISALIGNED, "%s: flags must be 16-byte aligned, the other buffers to "
                 "their element size", fn);
-  if (const gcg_status st = terms_layout(fn, n_tokens, hash_bits, true, &L)) return st;
-  if (n_tokens > 0 && workspace_bytes < L.total)
-    return fail(GCG_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, L.total);
+  if (const gcg_status st = terms_space(fn, n_tokens, hash_bits, workspace, true, &s)) return st;
+  if (n_tokens > 0)  // no token: no scratch, and the workspace may be NULL
+    if (const gcg_status st = check_workspace(fn, workspace, workspace_bytes, s.total, 8)) return st;
   hipStream_t st = static_cast<hipStream_t>(stream);
   GCG_HIP_CHECK(hipMemsetAsync(result_dev, 0, 16, st));
   if (n_tokens == 0) {
     GCG_HIP_CHECK(hipMemsetAsync(doc_ptr, 0, static_cast<size_t>(n_docs + 1) * 8, st));
     return GCG_OK;
   }
-  char* w = static_cast<char*>(workspace);
-  u64* key_a = reinterpret_cast<u64*>(w + L.off_key_a);
-  u64* key_b = reinterpret_cast<u64*>(w + L.off_key_b);
-  int32_t* idx_a = reinterpret_cast<int32_t*>(w + L.off_idx_a);
-  int32_t* idx_b = reinterpret_cast<int32_t*>(w + L.off_idx_b);
-  int32_t* tok_len = reinterpret_cast<int32_t*>(w + L.off_len);
-  int32_t* head = reinterpret_cast<int32_t*>(w + L.off_head);
-  int32_t* rep_tok = reinterpret_cast<int32_t*>(w + L.off_rep);
-  int32_t* is_first = reinterpret_cast<int32_t*>(w + L.off_first);
-  int32_t* first_id = reinterpret_cast<int32_t*>(w + L.off_fid);
-  int64_t* tok_start = reinterpret_cast<int64_t*>(w + L.off_start);
-  void* tmp = w + L.off_tmp;
   const int n = static_cast<int>(n_tokens);
   const int64_t n_tiles = tiles_of(n_bytes);
   const int nul_docs = doc_off == nullptr;
   hipLaunchKernelGGL(tokenize_spans_kernel, dim3(tile_grid(n_tiles)), dim3(kThreads), 0, st, n_bytes,
-                     flags, reinterpret_cast<const u64*>(tile_base), n_tiles, n_tokens, tok_start,
+                     flags, reinterpret_cast<const u64*>(tile_base), n_tiles, n_tokens, s.tok_start,
                      nul_docs, n_docs, doc_ptr);
   GCG_HIP_CHECK(hipGetLastError());
   if (!nul_docs) {
     hipLaunchKernelGGL(tokenize_doc_ptr_kernel, dim3(grid_for(n_docs + 1)), dim3(256), 0, st, n_docs,
-                       doc_off, n_tokens, tok_start, doc_ptr);
+                       doc_off, n_tokens, s.tok_start, doc_ptr);
     GCG_HIP_CHECK(hipGetLastError());
   }
   const u64 mask = hash_bits >= 64 ? ~u64{0} : ((u64{1} << hash_bits) - 1);
   hipLaunchKernelGGL(tokenize_hash_kernel, dim3(grid_for(n_tokens)), dim3(256), 0, st, n_bytes, text,
-                     flags, n_tokens, tok_start, mask, tok_len, key_a, idx_a);
+                     flags, n_tokens, s.tok_start, mask, s.tok_len, s.key_a, s.idx_a);
   GCG_HIP_CHECK(hipGetLastError());
-  size_t t = L.tmp_bytes;
-  GCG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, t, key_a, key_b, idx_a, idx_b, n, 0,
-                                                   static_cast<int>(hash_bits), st));
+  GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceRadixSort::SortPairs, s.key_a, s.key_b, s.idx_a, s.idx_b, n, 0,
+      static_cast<int>(hash_bits), st)));
   hipLaunchKernelGGL(tokenize_heads_kernel, dim3(grid_for(n_tokens)), dim3(256), 0, st, n_tokens,
-                     key_b, idx_a);
+                     s.key_b, s.idx_a);
   GCG_HIP_CHECK(hipGetLastError());
-  t = L.tmp_bytes;
-  GCG_HIP_CHECK(hipcub::DeviceScan::InclusiveScan(tmp, t, idx_a, head, hipcub::Max(), n, st));
+  GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceScan::InclusiveScan, s.idx_a, s.head, hipcub::Max(), n, st)));
   hipLaunchKernelGGL(tokenize_verify_kernel, dim3(grid_for(n_tokens)), dim3(256), 0, st, n_tokens,
-                     text, tok_start, tok_len, idx_b, head, rep_tok, is_first,
+                     text, s.tok_start, s.tok_len, s.idx_b, s.head, s.rep_tok, s.is_first,
                      reinterpret_cast<int32_t*>(result_dev + 1));
   GCG_HIP_CHECK(hipGetLastError());
-  t = L.tmp_bytes;
-  GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, t, is_first, first_id, n, st));
+  GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceScan::ExclusiveSum, s.is_first, s.first_id, n, st)));
   hipLaunchKernelGGL(tokenize_number_kernel, dim3(grid_for(n_tokens)), dim3(256), 0, st, n_tokens,
-                     tok_start, tok_len, rep_tok, is_first, first_id, tok_term, term_start, term_len,
+                     s.tok_start, s.tok_len, s.rep_tok, s.is_first, s.first_id, tok_term, term_start, term_len,
                      result_dev);
   GCG_HIP_CHECK(hipGetLastError());
   return GCG_OK;
@@ -542,9 +538,9 @@ gcg_status gcg_tokenize_remap_workspace_bytes(int64_t n_tokens, size_t* bytes) {
   const char* fn = "gcg_tokenize_remap_workspace_bytes";
   if (bytes == nullptr) return fail(GCG_ERR_INVALID_ARG, "%s: NULL bytes", fn);
   *bytes = 0;
-  size_t t = 0;
-  if (const gcg_status st = remap_sizes(fn, n_tokens, 0, 0, &t)) return st;
-  *bytes = 2 * align_up(static_cast<size_t>(n_tokens + 1) * 4, 256) + align_up(t, 256);
+  RemapSpace s;
+  if (const gcg_status st = remap_space(fn, n_tokens, 0, 0, nullptr, true, &s)) return st;
+  *bytes = s.total;
   return GCG_OK;
 }
 
@@ -553,9 +549,8 @@ gcg_status gcg_tokenize_remap(int64_t n_tokens, const int32_t* tok_term, int64_t
                               int32_t* tokens, int64_t* doc_ptr, void* workspace,
                               size_t workspace_bytes, gcg_stream_t stream) {
   const char* fn = "gcg_tokenize_remap";
-  size_t t = 0, need = 0;
-  if (const gcg_status st = remap_sizes(fn, n_tokens, n_docs, n_terms, &t)) return st;
-  if (const gcg_status st = gcg_tokenize_remap_workspace_bytes(n_tokens, &need)) return st;
+  RemapSpace s;
+  if (const gcg_status st = remap_space(fn, n_tokens, n_docs, n_terms, nullptr, false, &s)) return st;
   if (doc_ptr_in == nullptr || doc_ptr == nullptr || workspace == nullptr ||
       (n_tokens > 0 && (tok_term == nullptr || tokens == nullptr)) ||
       (n_terms > 0 && action == nullptr))
@@ -564,20 +559,17 @@ gcg_status gcg_tokenize_remap(int64_t n_tokens, const int32_t* tok_term, int64_t
   if (!aligned(tok_term, 4) || !aligned(action, 4) || !aligned(tokens, 4) ||
       !aligned(doc_ptr_in, 8) || !aligned(doc_ptr, 8) || !aligned(workspace, 8))
     return fail(GCG_ERR_MISALIGNED, "%s: a buffer is not aligned to its element size", fn);
-  if (workspace_bytes < need)
-    return fail(GCG_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, need);
+  if (const gcg_status st = remap_space(fn, n_tokens, n_docs, n_terms, workspace, true, &s))
+    return st;
+  if (const gcg_status st = check_workspace(fn, workspace, workspace_bytes, s.total, 8)) return st;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t n4 = align_up(static_cast<size_t>(n_tokens + 1) * 4, 256);
-  char* w = static_cast<char*>(workspace);
-  int32_t* keep = reinterpret_cast<int32_t*>(w);
-  int32_t* pos = reinterpret_cast<int32_t*>(w + n4);
   hipLaunchKernelGGL(tokenize_keep_kernel, dim3(grid_for(n_tokens + 1)), dim3(256), 0, st, n_tokens,
-                     tok_term, n_terms, action, keep);
+                     tok_term, n_terms, action, s.keep);
   GCG_HIP_CHECK(hipGetLastError());
-  GCG_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(w + 2 * n4, t, keep, pos,
-                                                 static_cast<int>(n_tokens + 1), st));
+  GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceScan::ExclusiveSum, s.keep, s.pos, static_cast<int>(n_tokens + 1),
+      st)));
   hipLaunchKernelGGL(tokenize_remap_kernel, dim3(grid_for(std::max(n_tokens, n_docs + 1))),
-                     dim3(256), 0, st, n_tokens, tok_term, action, keep, pos, tokens, n_docs,
+                     dim3(256), 0, st, n_tokens, tok_term, action, s.keep, s.pos, tokens, n_docs,
                      doc_ptr_in, doc_ptr);
   GCG_HIP_CHECK(hipGetLastError());
   return GCG_OK;
