@@ -13,10 +13,10 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_DIR = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
 # Translation units of libgcg_spmm.so: SpMM kernels + planner, the bf16-operand SpMM and its row
-# conversion, CSR utilities, graph build,
-# SpGEMM, MFMA dense projection + softmax/xent, Philox dropout, the mini-batch MLP's epoch
-# segmentation and W1 step, k-d-tree labels + geolocation metrics, the mixture-density location
-# head with the Gaussian layer of the inverse model, the softmax cross-entropy against sparse
+# conversion, CSR utilities, graph build, SpGEMM, the MFMA dense side in four files over
+# dense_shared.h (plain and f32-fused GEMM; NT GEMM; the bf16x6 fused output layer + softmax/xent
+# rows; split-K TN), Philox dropout, the mini-batch MLP's epoch segmentation and W1 step,
+# k-d-tree labels + geolocation metrics, the mixture-density location head with the Gaussian layer of the inverse model, the softmax cross-entropy against sparse
 # soft targets, the k-means initialisation of the Gaussian components, the dialect-embedding
 # evaluation (scaling, neighbour ranks, kneighbors), the row log-sum-exp and per-word column sums
 # of the location-to-language model's analyses, the TF-IDF features over token ids (counting,
@@ -24,11 +24,13 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 # in the UTF-8 bytes, the term dictionary), error/version helpers.
 # Compiled in parallel, linked into one shared library.
 SOURCES = [os.path.join(CSRC, f) for f in
-           ("spmm.hip", "spmm_bf16.hip", "csr_ops.hip", "graph_build.hip", "spgemm.hip", "dense.hip", "dropout.hip",
+           ("spmm.hip", "spmm_bf16.hip", "csr_ops.hip", "graph_build.hip", "spgemm.hip",
+            "dense_gemm.hip", "dense_nt.hip", "dense_fused.hip", "dense_tn.hip", "dropout.hip",
             "minibatch.hip", "geo.hip", "kmeans.hip", "mdn.hip", "softmax_csr.hip", "neighbours.hip",
             "vocab_stats.hip", "tfidf.hip", "tokenize.hip", "errors.cpp")]
 INTERNAL_HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "layout.h", "scratch.h",
-                                                    "spmm_shared.h", "index_kernels.h",
+                                                    "spmm_shared.h", "dense_shared.h",
+                                                    "index_kernels.h",
                                                     "gemm_epilogue.inc", "philox.h",
                                                     "rectify_backward_pass.inc",
                                                     "segment_kernels.h", "row_maxsum.h")]
@@ -39,12 +41,13 @@ ARCH = os.environ.get("GCG_OFFLOAD_ARCH", "gfx950")
 # -ffp-contract=off: every product and sum is rounded separately, as scipy's csr_matvecs does.
 HIPCC_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", f"--offload-arch={ARCH}",
                "-Wall", "-Wno-unused-command-line-argument"]
-# Per-file extra flags. dense.hip: no SLP vectorizer (round 6) -- it packed the NT GEMM's
+# Per-file extra flags. The dense files: no SLP vectorizer (round 6) -- it packed the NT GEMM's
 # epilogue (bias add, rectify) and fallback arithmetic into v_pk_add_f32 / v_pk_mul_f32, and a
 # packed f32 op beside another workgroup's MFMAs on the same SIMD costs far more than its issue
 # slot (MI355X_MICROARCH.md, "price of one filler beside MFMAs"): the bf16x6 projection 167 ->
 # 183-185 TF, dP 167 -> 175 on one box, bitwise the same results (profiles/r06/dense_ab.jsonl).
-FILE_FLAGS = {"dense.hip": ["-fno-slp-vectorize"]}
+FILE_FLAGS = {f: ["-fno-slp-vectorize"]
+              for f in ("dense_gemm.hip", "dense_nt.hip", "dense_fused.hip", "dense_tn.hip")}
 
 
 def _hipcc() -> str:

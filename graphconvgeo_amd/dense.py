@@ -7,7 +7,7 @@ Reference (Theano, host BLAS / CPU):
                                            T.mean(T.eq(out.argmax(-1), y))    mlpconv.py:227-253
     predict_proba                          softmax rows                       mlpconv.py:329-335
 
-Here every product runs in libgcg_spmm.so's MFMA kernels (csrc/dense.hip):
+Here every product runs in libgcg_spmm.so's MFMA kernels (csrc/dense_*.hip):
   matmul(A, W)                    C = A . W          gcg_gemm_nt on W^T (grad A: g . W^T,
                                   the same kernel on W); grad W on gemm_tn
   gemm(A, B) / gemm_nt(A, Bt)     the plain products (register-B / LDS-DMA kernels)

@@ -12,7 +12,7 @@ Reference (Lasagne `Layer` subclasses, Theano graph, host CPU):
 Here: torch modules with the same constructor arguments and `get_output_for` /
 `forward(input, target_indices=None)`. The sparse products run in the HIP kernels
 (graphconvgeo_amd.sparse.spmm) with bias + rectify + the target-row subset fused in the
-epilogue; the dense projection T.dot(h, W) runs on the hand-written f32 MFMA kernels of csrc/dense.hip
+epilogue; the dense projection T.dot(h, W) runs on the hand-written f32 MFMA kernels of csrc/dense_*.hip
 (forward and input gradient on the LDS-DMA NT GEMM, the weight gradient on the split-K
 kernel; the trainer's output layer is one fused MFMA kernel, graphconvgeo_amd.dense). Backward follows Theano's rules: grad of
 S.dot(A, Z) w.r.t. Z is A^T . gz (A^T = H when H is symmetric -- checked once on the device,

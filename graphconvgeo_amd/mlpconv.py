@@ -9,7 +9,7 @@ step over all N nodes (mlpconv.py:293-295):
               (HIP SpMM, fused rows), then the softmax-CE row kernel (loss, hits; gradient pass
               in backward)
             order "propagate_first": P = (H.h)[train_indices] (HIP SpMM), then ONE MFMA kernel
-              for P.W2 + b2, softmax, CE, argmax hits and the logits gradient (csrc/dense.hip)
+              for P.W2 + b2, softmax, CE, argmax hits and the logits gradient (csrc/dense_fused.hip)
   loss      mean categorical CE of softmax(logits) + L1/L2 shares on W (mlpconv.py:229-243)
   backward  Theano's rules through the HIP kernels (scatter-add, H.g, X^T.g)
   update    lasagne.updates.adam(lr=4e-3, 0.9, 0.999, 1e-8) (mlpconv.py:263), restated below

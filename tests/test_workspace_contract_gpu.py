@@ -1,4 +1,5 @@
-"""The size contract of every entry that works in a caller's workspace and runs hipcub: claiming
+"""The size contract of every entry that works in a caller's workspace and runs hipcub, and of
+the dense entries that keep bf16 planes or split-K partials in one: claiming
 one byte less than the entry reports is GCG_ERR_WORKSPACE, names the entry in gcg_last_error() and
 leaves the outputs alone; claiming exactly what it reports works. The buffer behind the claim always
 has the full size, so nothing can be written out of bounds. Tiny inputs, references in numpy."""
@@ -478,3 +479,93 @@ def test_kneighbors(native_lib, cuda, words):
     assert status.item() == 0
     np.testing.assert_array_equal(index.cpu().numpy(), order[:, :k])
     np.testing.assert_array_equal(dist.cpu().numpy(), np.take_along_axis(d2, order[:, :k], 1))
+
+
+# ---- dense: M = 9 rows, N = 5 columns, K = 33 (two 32-deep chunks, the second with one live k) ----
+
+MATH_F32, MATH_BF16X6 = 0, 1
+DENSE_BAR = 2.0 ** -20  # of sum_k |a||b| per element: test_dense_gpu.py's bar for both maths
+
+
+def padded(a, ld):
+    """`a` in rows of ld floats (ld % 4 == 0, as the dwordx4 reads need), zeros behind."""
+    p = np.zeros((a.shape[0], ld), np.float32)
+    p[:, :a.shape[1]] = a
+    return p
+
+
+@pytest.fixture(scope="module")
+def dense_case():
+    rng = np.random.default_rng(11)
+    M, N, K = 9, 5, 33
+    A = rng.standard_normal((M, K)).astype(np.float32)
+    W = rng.standard_normal((K, N)).astype(np.float32)
+    prod = A.astype(np.float64) @ W.astype(np.float64)
+    absprod = np.abs(A).astype(np.float64) @ np.abs(W).astype(np.float64)
+    return A, W, prod, absprod
+
+
+def test_gemm_nt_bf16x6(native_lib, cuda, dense_case):
+    lib = native_lib
+    A, W, prod, absprod = dense_case
+    (M, K), N = A.shape, W.shape[1]
+    need = lib.gcg_gemm_nt_workspace(N, K, MATH_BF16X6)
+    assert need == N * 2 * 192
+    a, bt = dev(padded(A, 36), cuda), dev(padded(W.T, 36), cuda)
+    c = out((M, 8), torch.float32, cuda)
+    run_contract(lib, cuda, "gcg_gemm_nt", need,
+                 lambda ws, b: lib.gcg_gemm_nt(M, N, K, ptr(a), 36, ptr(bt), 36, None, 0, ptr(c), 8,
+                                               MATH_BF16X6, 0, ptr(ws), b, None), [c])
+    err = np.abs(c.cpu().numpy()[:, :N].astype(np.float64) - prod)
+    assert (err <= DENSE_BAR * absprod).all(), (err / absprod).max()
+
+
+@pytest.mark.parametrize("math", [MATH_F32, MATH_BF16X6])
+def test_gemm_tn(native_lib, cuda, math):
+    lib = native_lib
+    rng = np.random.default_rng(12)
+    R, M, N = 40, 3, 5
+    A = rng.standard_normal((R, M)).astype(np.float32)
+    B = rng.standard_normal((R, N)).astype(np.float32)
+    need = reported(lib, "gcg_gemm_tn_workspace_bytes", R, M, N, math, 0)
+    a, b_ = dev(padded(A, 4), cuda), dev(padded(B, 8), cuda)
+    c = out((M, 8), torch.float32, cuda)
+    run_contract(lib, cuda, "gcg_gemm_tn", need,
+                 lambda ws, b: lib.gcg_gemm_tn(R, M, N, ptr(a), 4, ptr(b_), 8, None, ptr(c), 8, math, 0,
+                                               ptr(ws), b, None), [c])
+    prod = A.T.astype(np.float64) @ B.astype(np.float64)
+    absprod = np.abs(A.T).astype(np.float64) @ np.abs(B).astype(np.float64)
+    err = np.abs(c.cpu().numpy()[:, :N].astype(np.float64) - prod)
+    assert (err <= DENSE_BAR * absprod).all(), (err / absprod).max()
+
+
+def test_project_softmax_xent_bf16x6(native_lib, cuda, dense_case):
+    lib = native_lib
+    A, W, logits, absprod = dense_case
+    (M, K), N = A.shape, W.shape[1]
+    labels = (np.arange(M) % N).astype(np.int32)
+    scale = 0.25
+    need = lib.gcg_project_softmax_xent_workspace(N, K, MATH_BF16X6)
+    assert need == 1024 * 2 * 192
+    a, w, y = dev(padded(A, 36), cuda), dev(padded(W, 8), cuda), dev(labels, cuda)
+    o, loss, hit = (out((M, 8), torch.float32, cuda), out(M, torch.float32, cuda),
+                    out(M, torch.float32, cuda))
+    run_contract(lib, cuda, "gcg_project_softmax_xent", need,
+                 lambda ws, b: lib.gcg_project_softmax_xent(
+                     M, N, K, ptr(a), 36, ptr(w), 8, None, ptr(y), scale, None, ptr(o), 8, ptr(loss),
+                     ptr(hit), None, MATH_BF16X6, 0, ptr(ws), b, None), [o, loss, hit])
+    z = logits - logits.max(1, keepdims=True)
+    p = np.exp(z) / np.exp(z).sum(1, keepdims=True)
+    onehot = np.eye(N)[labels]
+    err = np.abs(o.cpu().numpy()[:, :N].astype(np.float64) - (p - onehot) * scale)
+    assert (err <= DENSE_BAR * absprod).all(), (err / absprod).max()
+    # The element bar above is the one test_dense_gpu.py uses. The two row outputs have none of
+    # their own there; this one is derived here: the loss is a difference of two values (the
+    # log-sum-exp and the label's logit) that each follow the logits, so twice the logits' bar,
+    # taken over the row. The hits are checked only on logits further apart than that.
+    row_bar = 2 * DENSE_BAR * absprod.max(1)
+    want_loss = np.log(np.exp(z).sum(1)) - z[np.arange(M), labels]
+    assert (np.abs(loss.cpu().numpy() - want_loss) <= row_bar).all()
+    top2 = np.sort(logits, 1)[:, -2:]
+    assert (top2[:, 1] - top2[:, 0] > row_bar).all()
+    np.testing.assert_array_equal(hit.cpu().numpy(), logits.argmax(1) == labels)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Timings of the dense output-layer products on one MI355X: the MFMA kernels of
-csrc/dense.hip against torch (hipBLASLt GEMM + eager softmax/CE), HIP events, same stream.
+csrc/dense_*.hip against torch (hipBLASLt GEMM + eager softmax/CE), HIP events, same stream.
 
 Shapes (Twitter-World, SURVEY.md §8d: K = 300 hidden, C = 930 classes, T = 60 % of N rows):
   proj      logits = P . W2 + b2        T x 300 . 300 x 930   (propagate-first order)
