@@ -15,6 +15,9 @@ the graph work and the training on the GPU:
   GPU   --device-tokenizer (with --device-tfidf): tfidf.tokenize_corpus_device finds the tokens
         in the UTF-8 bytes and builds the term dictionary in HIP; the host lowers, joins and
         encodes the corpus and handles each distinct term once
+  GPU   --device-mentions: mentions.mention_incidences_device finds the @mentions in the UTF-8
+        bytes in HIP as well; the host looks each distinct name up once, and the incidences,
+        the projected edges and H stay on the device
 
 Synthetic data: users live in one of `regions`; they mention other users mostly from their
 own region and use region-specific words, so the graph and the text both carry the label.
@@ -74,6 +77,8 @@ def main():
     ap.add_argument("--device-tokenizer", action="store_true",
                     help="with --device-tfidf: tokenise on the GPU as well "
                          "(tfidf.tokenize_corpus_device)")
+    ap.add_argument("--device-mentions", action="store_true",
+                    help="parse the @mentions on the GPU (mentions.mention_incidences_device)")
     args = ap.parse_args()
     if args.device_tokenizer and not args.device_tfidf:
         ap.error("--device-tokenizer needs --device-tfidf")
@@ -87,7 +92,7 @@ def main():
     (df_train, df_dev, df_test), regions = synthetic_tables(args.users)
     t0 = time.perf_counter()
     H = mention_graph_operator(df_train, df_dev, df_test, celebrity_threshold=args.celebrity,
-                               device="cuda")
+                               device="cuda", parser="device" if args.device_mentions else "host")
     t_graph = time.perf_counter() - t0
     t0 = time.perf_counter()
     if args.device_tfidf:
@@ -130,6 +135,8 @@ def main():
            "graph_build_s": round(t_graph, 3), "fit_s": round(t_fit, 3),
            "epochs_run": len(clf.history), "test_acc": round(acc, 4),
            "chance": round(1.0 / regions, 4)}
+    if args.device_mentions:
+        rec.update(mentions="device")
     if args.device_tfidf:
         rec.update(tfidf="device", tfidf_s=round(t_tfidf, 3), tokenizer=vec.tokenizer,
                    tokenize_s=round(vec.tokenize_s_, 3))

@@ -21,7 +21,8 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 # evaluation (scaling, neighbour ranks, kneighbors), the row log-sum-exp and per-word column sums
 # of the location-to-language model's analyses, the TF-IDF features over token ids (counting,
 # document frequencies, pruning, weighting), tokenising the corpus for them (marking the tokens
-# in the UTF-8 bytes, the term dictionary), error/version helpers.
+# in the UTF-8 bytes, the term dictionary) and by the same stages the @mentions of the mention
+# graph, error/version helpers.
 # Compiled in parallel, linked into one shared library.
 SOURCES = [os.path.join(CSRC, f) for f in
            ("spmm.hip", "spmm_bf16.hip", "csr_ops.hip", "graph_build.hip", "spgemm.hip",

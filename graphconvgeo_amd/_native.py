@@ -206,6 +206,11 @@ SIGNATURES = {
                                      _p, _p, C.c_size_t, _p]),
     "gcg_tokenize_remap_workspace_bytes": (C.c_int, [_i64, _psz]),
     "gcg_tokenize_remap": (C.c_int, [_i64, _p, _i64, _p, _i64, _p, _p, _p, _p, C.c_size_t, _p]),
+    # the @mentions by the same stages (mentions.py)
+    "gcg_mention_mark_workspace_bytes": (C.c_int, [_i64, _psz]),
+    "gcg_mention_mark": (C.c_int, [_i64, _p, _p, _p, _p, _p, C.c_size_t, _p]),
+    "gcg_tokenize_terms_folded": (C.c_int, [_i64, _p, _p, _p, _i64, _i64, _p, C.c_int32, C.c_int32,
+                                            _p, _p, _p, _p, _p, _p, C.c_size_t, _p]),
     "gcg_spgemm_ex": (C.c_int, [_i64, _i64, _i64, _i64, _p, _p, _p, C.c_int, _i64, _p, _p, _p,
                                 C.c_int, _i64, _p, _p, _p, _p, C.c_int32, _i64, _p]),
 }

@@ -12,6 +12,11 @@
 // dictionary (ids in order of first appearance), exact whatever the hash does because every token
 // is compared byte by byte with its run's representative. remap: the host's per-term action
 // (drop, -1, column) and the final doc_ptr. Integers only; no atomics that carry a value.
+//
+// The same stages parse the @mentions of the mention graph (graphconvgeo_amd/mentions.py,
+// mention_incidences_device): the marking's other rule flags the names the regex of data.py:311
+// finds, a rule over three ASCII byte classes, and the dictionary folds A-Z where it hashes and
+// compares, so that the spellings of one name are one term.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -53,10 +58,39 @@ __device__ __forceinline__ bool is_word(uint32_t cp, const uint32_t* ascii,
   return (table[cp >> 5] >> (cp & 31u)) & 1u;
 }
 
+// The byte classes of the mention regex (?<=^|(?<=[^a-zA-Z0-9-_\.]))@([A-Za-z]+[A-Za-z0-9_]+):
+// L = [A-Za-z], N = L, digits and '_' (a name's bytes), P = N, '-' and '.' (what may not precede
+// the '@'). All ASCII: no byte of a multi-byte code point is in any of them.
+__device__ __forceinline__ bool is_letter(uint32_t b) { return ((b | 0x20u) - 'a') < 26u; }
+__device__ __forceinline__ bool is_name(uint32_t b) {
+  return is_letter(b) || (b - '0') < 10u || b == '_';
+}
+__device__ __forceinline__ bool is_before_name(uint32_t b) {
+  return is_name(b) || b == '-' || b == '.';
+}
+
+// The flag of byte s[0] under the mention rule; s[-2] .. s[1] are read. '@' opens a mention
+// where the byte before it is not in P (a document's first '@' follows a NUL, or the start of
+// the text, which reads as NUL) and a letter and a name byte follow; the name is the run of N
+// from the letter on, so it starts here where s[-1] is such an '@' and ends at the first byte
+// outside N. Runs of N that are no name end with kRunEnd too: only what follows a kStart is read.
+__device__ __forceinline__ uint8_t mention_flag(const uint8_t* s) {
+  const uint32_t b = s[0];
+  uint8_t f = 0;
+  if (is_name(b)) {
+    if (is_letter(b) && s[-1] == '@' && !is_before_name(s[-2]) && is_name(s[1])) f = kStart;
+  } else if (is_name(s[-1])) {
+    f = kRunEnd;
+  }
+  return b == 0 ? f | kNul : f;
+}
+
 // One tile per workgroup. The tile and its halo go to LDS with one 16-byte load per lane; bytes
 // outside [0, n) read as NUL, so the text starts and ends as a document does. Byte p of the tile
 // is lane p % 256's, so a wave reads 64 consecutive LDS bytes. flags[g] for every g below
-// round16(n); cnt[tile] = token starts | NULs << 32.
+// round16(n); cnt[tile] = token starts | NULs << 32. kMentions: the mention rule instead of the
+// word runs (no table, no lookbehind).
+template <bool kMentions>
 __global__ __launch_bounds__(kThreads) void tokenize_mark_kernel(
     int64_t n, const uint8_t* __restrict__ text, const uint32_t* __restrict__ table, int lookbehind,
     uint8_t* __restrict__ flags, u64* __restrict__ cnt, int64_t n_tiles) {
@@ -79,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void tokenize_mark_kernel(
       const int64_t g = t0 + off;
       s[off] = (g >= 0 && g < n) ? text[g] : uint8_t{0};
     }
-    if (threadIdx.x < 4) ascii[threadIdx.x] = table[threadIdx.x];
+    if (!kMentions && threadIdx.x < 4) ascii[threadIdx.x] = table[threadIdx.x];
     if (threadIdx.x == 0) { n_start = 0; n_nul = 0; }
     __syncthreads();
     if (t0 + kTile > n) {  // the last tile: what the 16-byte loads brought in past n is NUL
@@ -95,7 +129,9 @@ __global__ __launch_bounds__(kThreads) void tokenize_mark_kernel(
       if (g >= n16) break;
       uint8_t f = 0;
       const uint32_t b = s[p];
-      if (g < n && !is_cont(b)) {
+      if (kMentions) {
+        if (g < n) f = mention_flag(s + p);
+      } else if (g < n && !is_cont(b)) {
         int len, plen, nlen;
         const uint32_t cp = decode(s + p, &len);
         const bool w = is_word(cp, ascii, table);
@@ -207,8 +243,16 @@ __device__ __forceinline__ u64 fmix64(u64 h) {
   return h ^ (h >> 33);
 }
 
+// A byte as the dictionary sees it: with kFold, ASCII A-Z as a-z (no other byte changes, so a
+// multi-byte code point stays itself).
+template <bool kFold>
+__device__ __forceinline__ uint32_t term_byte(uint32_t b) {
+  return (kFold && (b - 'A') < 26u) ? b | 0x20u : b;
+}
+
 // One lane per token: walk its bytes to the run's end (FNV-1a, then a finaliser so the low bits
 // the sort may be cut to depend on every byte).
+template <bool kFold>
 __global__ void tokenize_hash_kernel(int64_t n, const uint8_t* __restrict__ text,
                                      const uint8_t* __restrict__ flags, int64_t n_tokens,
                                      const int64_t* __restrict__ tok_start, u64 mask,
@@ -220,7 +264,7 @@ __global__ void tokenize_hash_kernel(int64_t n, const uint8_t* __restrict__ text
     int64_t j = s;
     u64 h = 0xcbf29ce484222325ull;
     do {
-      h = (h ^ text[j]) * 0x100000001b3ull;
+      h = (h ^ term_byte<kFold>(text[j])) * 0x100000001b3ull;
       ++j;
     } while (j < n && !(flags[j] & kRunEnd) && j - s < INT32_MAX);
     tok_len[k] = static_cast<int32_t>(j - s);
@@ -239,7 +283,9 @@ __global__ void tokenize_heads_kernel(int64_t n_tokens, const u64* __restrict__ 
 }
 
 // Sorted position j: its token against the run's first token (the sort is stable, so that is the
-// term's first occurrence), byte by byte. Different bytes under one hash set *collision.
+// term's first occurrence), byte by byte (as the hash saw them: folded with kFold). Different
+// bytes under one hash set *collision.
+template <bool kFold>
 __global__ void tokenize_verify_kernel(int64_t n_tokens, const uint8_t* __restrict__ text,
                                        const int64_t* __restrict__ tok_start,
                                        const int32_t* __restrict__ tok_len,
@@ -257,7 +303,8 @@ __global__ void tokenize_verify_kernel(int64_t n_tokens, const uint8_t* __restri
     bool same = len == tok_len[r];
     const uint8_t* a = text + tok_start[t];
     const uint8_t* b = text + tok_start[r];
-    for (int32_t i = 0; same && i < len; ++i) same = a[i] == b[i];
+    for (int32_t i = 0; same && i < len; ++i)
+      same = term_byte<kFold>(a[i]) == term_byte<kFold>(b[i]);
     if (!same) atomicOr(collision, 1);
   }
 }
@@ -404,14 +451,7 @@ gcg_status remap_space(const char* fn, int64_t n_tokens, int64_t n_docs, int64_t
   return ts.take_exact(fn, cv, &s->tmp, &s->total);
 }
 
-}  // namespace
-
-extern "C" {
-
-int32_t gcg_tokenize_tile_bytes(void) { return kTile; }
-
-gcg_status gcg_tokenize_mark_workspace_bytes(int64_t n_bytes, size_t* bytes) {
-  const char* fn = "gcg_tokenize_mark_workspace_bytes";
+gcg_status mark_bytes(const char* fn, int64_t n_bytes, size_t* bytes) {
   if (bytes == nullptr) return fail(GCG_ERR_INVALID_ARG, "%s: NULL bytes", fn);
   *bytes = 0;
   MarkSpace s;
@@ -420,15 +460,15 @@ gcg_status gcg_tokenize_mark_workspace_bytes(int64_t n_bytes, size_t* bytes) {
   return GCG_OK;
 }
 
-gcg_status gcg_tokenize_mark(int64_t n_bytes, const uint8_t* text, const uint32_t* word_table,
-                             int32_t lookbehind, uint8_t* flags, uint64_t* tile_base,
-                             int64_t* totals_dev, void* workspace, size_t workspace_bytes,
-                             gcg_stream_t stream) {
-  const char* fn = "gcg_tokenize_mark";
+// The marking under either rule: word runs by `word_table` and `lookbehind`, or with `mentions`
+// the mention rule, which takes neither.
+gcg_status mark(const char* fn, bool mentions, int64_t n_bytes, const uint8_t* text,
+                const uint32_t* word_table, int32_t lookbehind, uint8_t* flags, uint64_t* tile_base,
+                int64_t* totals_dev, void* workspace, size_t workspace_bytes, gcg_stream_t stream) {
   MarkSpace s;
   if (const gcg_status st = mark_space(fn, n_bytes, nullptr, false, &s)) return st;
-  if (word_table == nullptr || tile_base == nullptr || totals_dev == nullptr || workspace == nullptr ||
-      (n_bytes > 0 && (text == nullptr || flags == nullptr)))
+  if ((!mentions && word_table == nullptr) || tile_base == nullptr || totals_dev == nullptr ||
+      workspace == nullptr || (n_bytes > 0 && (text == nullptr || flags == nullptr)))
     return fail(GCG_ERR_INVALID_ARG, "%s: NULL text, word_table, flags, tile_base, totals_dev or "
                 "workspace", fn);
   if (!aligned(text, 16) || !aligned(flags, 16) || !aligned(word_table, 4) ||
@@ -442,8 +482,9 @@ gcg_status gcg_tokenize_mark(int64_t n_bytes, const uint8_t* text, const uint32_
   const int64_t n_tiles = tiles_of(n_bytes);
   GCG_HIP_CHECK(hipMemsetAsync(s.cnt + n_tiles, 0, 8, st));
   if (n_tiles > 0) {
-    hipLaunchKernelGGL(tokenize_mark_kernel, dim3(tile_grid(n_tiles)), dim3(kThreads), 0, st,
-                       n_bytes, text, word_table, lookbehind != 0, flags, s.cnt, n_tiles);
+    hipLaunchKernelGGL(mentions ? tokenize_mark_kernel<true> : tokenize_mark_kernel<false>,
+                       dim3(tile_grid(n_tiles)), dim3(kThreads), 0, st, n_bytes, text, word_table,
+                       lookbehind != 0, flags, s.cnt, n_tiles);
     GCG_HIP_CHECK(hipGetLastError());
   }
   GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceScan::ExclusiveSum, s.cnt, reinterpret_cast<u64*>(tile_base),
@@ -454,23 +495,12 @@ gcg_status gcg_tokenize_mark(int64_t n_bytes, const uint8_t* text, const uint32_
   return GCG_OK;
 }
 
-gcg_status gcg_tokenize_terms_workspace_bytes(int64_t n_tokens, int32_t hash_bits, size_t* bytes) {
-  const char* fn = "gcg_tokenize_terms_workspace_bytes";
-  if (bytes == nullptr) return fail(GCG_ERR_INVALID_ARG, "%s: NULL bytes", fn);
-  *bytes = 0;
-  TermsSpace s;
-  if (const gcg_status st = terms_space(fn, n_tokens, hash_bits, nullptr, true, &s)) return st;
-  *bytes = s.total;
-  return GCG_OK;
-}
-
-gcg_status gcg_tokenize_terms(int64_t n_bytes, const uint8_t* text, const uint8_t* flags,
-                              const uint64_t* tile_base, int64_t n_tokens, int64_t n_docs,
-                              const int64_t* doc_off, int32_t hash_bits, int64_t* doc_ptr,
-                              int32_t* tok_term, int64_t* term_start, int32_t* term_len,
-                              int64_t* result_dev, void* workspace, size_t workspace_bytes,
-                              gcg_stream_t stream) {
-  const char* fn = "gcg_tokenize_terms";
+// The term dictionary; with `fold` A-Z and a-z are one byte to the hash and the comparison.
+gcg_status terms(const char* fn, bool fold, int64_t n_bytes, const uint8_t* text,
+                 const uint8_t* flags, const uint64_t* tile_base, int64_t n_tokens, int64_t n_docs,
+                 const int64_t* doc_off, int32_t hash_bits, int64_t* doc_ptr, int32_t* tok_term,
+                 int64_t* term_start, int32_t* term_len, int64_t* result_dev, void* workspace,
+                 size_t workspace_bytes, gcg_stream_t stream) {
   TermsSpace s;
   if (const gcg_status st = terms_space(fn, n_tokens, hash_bits, nullptr, false, &s)) return st;
   if (n_bytes < 0 || n_bytes > (int64_t{1} << 33) || n_docs < 1 || n_docs >= INT32_MAX)
@@ -513,8 +543,9 @@ gcg_status gcg_tokenize_terms(int64_t n_bytes, const uint8_t* text, const uint8_
     GCG_HIP_CHECK(hipGetLastError());
   }
   const u64 mask = hash_bits >= 64 ? ~u64{0} : ((u64{1} << hash_bits) - 1);
-  hipLaunchKernelGGL(tokenize_hash_kernel, dim3(grid_for(n_tokens)), dim3(256), 0, st, n_bytes, text,
-                     flags, n_tokens, s.tok_start, mask, s.tok_len, s.key_a, s.idx_a);
+  hipLaunchKernelGGL(fold ? tokenize_hash_kernel<true> : tokenize_hash_kernel<false>,
+                     dim3(grid_for(n_tokens)), dim3(256), 0, st, n_bytes, text, flags, n_tokens,
+                     s.tok_start, mask, s.tok_len, s.key_a, s.idx_a);
   GCG_HIP_CHECK(hipGetLastError());
   GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceRadixSort::SortPairs, s.key_a, s.key_b, s.idx_a, s.idx_b, n, 0,
       static_cast<int>(hash_bits), st)));
@@ -522,8 +553,9 @@ gcg_status gcg_tokenize_terms(int64_t n_bytes, const uint8_t* text, const uint8_
                      s.key_b, s.idx_a);
   GCG_HIP_CHECK(hipGetLastError());
   GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceScan::InclusiveScan, s.idx_a, s.head, hipcub::Max(), n, st)));
-  hipLaunchKernelGGL(tokenize_verify_kernel, dim3(grid_for(n_tokens)), dim3(256), 0, st, n_tokens,
-                     text, s.tok_start, s.tok_len, s.idx_b, s.head, s.rep_tok, s.is_first,
+  hipLaunchKernelGGL(fold ? tokenize_verify_kernel<true> : tokenize_verify_kernel<false>,
+                     dim3(grid_for(n_tokens)), dim3(256), 0, st, n_tokens, text, s.tok_start,
+                     s.tok_len, s.idx_b, s.head, s.rep_tok, s.is_first,
                      reinterpret_cast<int32_t*>(result_dev + 1));
   GCG_HIP_CHECK(hipGetLastError());
   GCG_HIP_CHECK(s.tmp.run(GCG_CUB(DeviceScan::ExclusiveSum, s.is_first, s.first_id, n, st)));
@@ -532,6 +564,67 @@ gcg_status gcg_tokenize_terms(int64_t n_bytes, const uint8_t* text, const uint8_
                      result_dev);
   GCG_HIP_CHECK(hipGetLastError());
   return GCG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t gcg_tokenize_tile_bytes(void) { return kTile; }
+
+gcg_status gcg_tokenize_mark_workspace_bytes(int64_t n_bytes, size_t* bytes) {
+  return mark_bytes("gcg_tokenize_mark_workspace_bytes", n_bytes, bytes);
+}
+
+gcg_status gcg_tokenize_mark(int64_t n_bytes, const uint8_t* text, const uint32_t* word_table,
+                             int32_t lookbehind, uint8_t* flags, uint64_t* tile_base,
+                             int64_t* totals_dev, void* workspace, size_t workspace_bytes,
+                             gcg_stream_t stream) {
+  return mark("gcg_tokenize_mark", false, n_bytes, text, word_table, lookbehind, flags, tile_base,
+              totals_dev, workspace, workspace_bytes, stream);
+}
+
+gcg_status gcg_mention_mark_workspace_bytes(int64_t n_bytes, size_t* bytes) {
+  return mark_bytes("gcg_mention_mark_workspace_bytes", n_bytes, bytes);
+}
+
+gcg_status gcg_mention_mark(int64_t n_bytes, const uint8_t* text, uint8_t* flags,
+                            uint64_t* tile_base, int64_t* totals_dev, void* workspace,
+                            size_t workspace_bytes, gcg_stream_t stream) {
+  return mark("gcg_mention_mark", true, n_bytes, text, nullptr, 0, flags, tile_base, totals_dev,
+              workspace, workspace_bytes, stream);
+}
+
+gcg_status gcg_tokenize_terms_workspace_bytes(int64_t n_tokens, int32_t hash_bits, size_t* bytes) {
+  const char* fn = "gcg_tokenize_terms_workspace_bytes";
+  if (bytes == nullptr) return fail(GCG_ERR_INVALID_ARG, "%s: NULL bytes", fn);
+  *bytes = 0;
+  TermsSpace s;
+  if (const gcg_status st = terms_space(fn, n_tokens, hash_bits, nullptr, true, &s)) return st;
+  *bytes = s.total;
+  return GCG_OK;
+}
+
+gcg_status gcg_tokenize_terms(int64_t n_bytes, const uint8_t* text, const uint8_t* flags,
+                              const uint64_t* tile_base, int64_t n_tokens, int64_t n_docs,
+                              const int64_t* doc_off, int32_t hash_bits, int64_t* doc_ptr,
+                              int32_t* tok_term, int64_t* term_start, int32_t* term_len,
+                              int64_t* result_dev, void* workspace, size_t workspace_bytes,
+                              gcg_stream_t stream) {
+  return terms("gcg_tokenize_terms", false, n_bytes, text, flags, tile_base, n_tokens, n_docs,
+               doc_off, hash_bits, doc_ptr, tok_term, term_start, term_len, result_dev, workspace,
+               workspace_bytes, stream);
+}
+
+gcg_status gcg_tokenize_terms_folded(int64_t n_bytes, const uint8_t* text, const uint8_t* flags,
+                                     const uint64_t* tile_base, int64_t n_tokens, int64_t n_docs,
+                                     const int64_t* doc_off, int32_t hash_bits, int32_t fold_ascii,
+                                     int64_t* doc_ptr, int32_t* tok_term, int64_t* term_start,
+                                     int32_t* term_len, int64_t* result_dev, void* workspace,
+                                     size_t workspace_bytes, gcg_stream_t stream) {
+  return terms("gcg_tokenize_terms_folded", fold_ascii != 0, n_bytes, text, flags, tile_base,
+               n_tokens, n_docs, doc_off, hash_bits, doc_ptr, tok_term, term_start, term_len,
+               result_dev, workspace, workspace_bytes, stream);
 }
 
 gcg_status gcg_tokenize_remap_workspace_bytes(int64_t n_tokens, size_t* bytes) {

@@ -79,10 +79,21 @@ def csr_from_edges(n: int, u: np.ndarray, v: np.ndarray, dtype=np.float32,
     return sps.csr_matrix((data, cols.astype(idx_t), indptr.astype(idx_t)), shape=(n, n))
 
 
+def device_ids(x, dev):
+    """Node ids as a contiguous int32 tensor on `dev`: an array or a list is uploaded, a tensor
+    that is already there is used where it lies."""
+    import torch
+
+    if isinstance(x, torch.Tensor):
+        return x.to(device=dev, dtype=torch.int32).contiguous()
+    return torch.as_tensor(np.asarray(x), dtype=torch.int32).to(dev).contiguous()
+
+
 def normalize_edges_device(n: int, u, v, device="cuda", self_loops: bool = True):
     """tensormain.py:170-180 on the GPU: undirected edges -> DeviceCSR H (canonical order,
     duplicates collapsed), values bitwise equal to `csr_from_edges` / the reference's
-    float64 D*adj*D cast to float32 (gcg_normalize_adjacency_f32). One sync to read nnz."""
+    float64 D*adj*D cast to float32 (gcg_normalize_adjacency_f32). `u`, `v`: arrays, or
+    tensors already on the device. One sync to read nnz."""
     import ctypes as C
 
     import torch
@@ -93,8 +104,7 @@ def normalize_edges_device(n: int, u, v, device="cuda", self_loops: bool = True)
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError("normalize_edges_device builds H in HBM: device must be a CUDA (HIP) device")
-    ut = torch.as_tensor(np.asarray(u), dtype=torch.int32).to(dev).contiguous()
-    vt = torch.as_tensor(np.asarray(v), dtype=torch.int32).to(dev).contiguous()
+    ut, vt = device_ids(u, dev), device_ids(v, dev)
     if ut.shape != vt.shape:
         raise ValueError("u and v must have the same length")
     e = int(ut.numel())

@@ -1359,6 +1359,39 @@ gcg_status gcg_tokenize_remap(int64_t n_tokens, const int32_t* tok_term, int64_t
                               const int32_t* action, int64_t n_docs, const int64_t* doc_ptr_in,
                               int32_t* tokens, int64_t* doc_ptr, void* workspace,
                               size_t workspace_bytes, gcg_stream_t stream);
+/*
+ * The @mentions of the mention graph by the same stages (graphconvgeo_amd/mentions.py,
+ * mention_incidences_device): the regex (?<=^|(?<=[^a-zA-Z0-9-_\.]))@([A-Za-z]+[A-Za-z0-9_]+)
+ * of the reference's data.py:311 as a rule over bytes. With L = [A-Za-z], N = [A-Za-z0-9_] and
+ * P = N, '-' and '.', the byte '@' opens a mention iff the byte before it is not in P (or it is
+ * the first byte of its document), the byte after it is in L and the one after that in N; the
+ * name is the maximal run of N from the byte after the '@'. The classes are ASCII, so the rule
+ * over UTF-8 bytes is the rule over code points. `text` as for gcg_tokenize_mark but NOT
+ * lowercased: lowering changes what matches (U+212A becomes 'k').
+ *
+ * gcg_mention_mark: the outputs of gcg_tokenize_mark (same sizes, same workspace size), a token
+ * being a name: its start is the byte after the '@'. They go to gcg_tokenize_terms_folded.
+ *
+ * gcg_tokenize_terms_folded: gcg_tokenize_terms, and with fold_ascii != 0 the bytes A-Z are
+ * hashed and compared as a-z, so the spellings of a name are one term, numbered where the
+ * first of them appears; term_start / term_len are that first spelling's (the caller lowers
+ * it). The comparison stays exact: names that differ after folding under one hash set
+ * result_dev[1]. fold_ascii = 0 is gcg_tokenize_terms. The workspace is
+ * gcg_tokenize_terms_workspace_bytes'.
+ *
+ * The incidences are then a remap (action = the node id of each name) and a gcg_tfidf_count
+ * over the remapped tokens: its indices are each document's distinct ids in ascending order.
+ */
+gcg_status gcg_mention_mark_workspace_bytes(int64_t n_bytes, size_t* bytes);
+gcg_status gcg_mention_mark(int64_t n_bytes, const uint8_t* text, uint8_t* flags,
+                            uint64_t* tile_base, int64_t* totals_dev, void* workspace,
+                            size_t workspace_bytes, gcg_stream_t stream);
+gcg_status gcg_tokenize_terms_folded(int64_t n_bytes, const uint8_t* text, const uint8_t* flags,
+                                     const uint64_t* tile_base, int64_t n_tokens, int64_t n_docs,
+                                     const int64_t* doc_off, int32_t hash_bits, int32_t fold_ascii,
+                                     int64_t* doc_ptr, int32_t* tok_term, int64_t* term_start,
+                                     int32_t* term_len, int64_t* result_dev, void* workspace,
+                                     size_t workspace_bytes, gcg_stream_t stream);
 
 #ifdef __cplusplus
 }

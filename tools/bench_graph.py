@@ -11,6 +11,15 @@ host computation on the same inputs (and checked equal to it):
   project     celebrity filter + co-mention projection (data.py:226-250, 364-370)
               GPU: mentions.project_mentions (gcg_project_mention_graph)
               CPU: oracle.project_mentions (pure-Python restatement of the reference's loops)
+  parse       the user texts to the mention incidences (data.py:302-362), and on to H
+              GPU: mentions.mention_incidences_device, whole and split by its `timings` (prep_s =
+                   join and encode, upload_s, kernels_s, terms_s = the per-name host work), and
+                   mention_graph_operator(parser="device")
+              CPU: mentions.mention_incidences on the same tables in the same run, and
+                   mention_graph_operator(parser="host"); the results are checked equal
+              Synthetic tables, seed 7: every user has 100 tokens of 10 bytes, 6 of them
+              mentions drawn as mention_incidences_synth draws ids (Zipf-like over the users
+              and half as many mention-only names), a fifth of them spelt in upper case.
 
 Prints one JSON line per measurement.
 """
@@ -133,9 +142,96 @@ def bench_project(n_users, dev, cpu: bool, thr=10):
     emit(rec)
 
 
+_B36 = np.frombuffer(b"0123456789abcdefghijklmnopqrstuvwxyz", np.uint8)
+
+
+def mention_tables_synth(n_users, per_user=6, per_doc=100, n_words=500_000, seed=7):
+    """(df_train, df_dev, df_test): users u0000000, u0000001, ... (base 36, so sorted), each
+    with `per_doc` tokens of 10 bytes: words, and at random places `per_user` mentions of the
+    ids mention_incidences_synth draws, '@' and the name of a user or of a mention-only name."""
+    import pandas as pd
+
+    n_users, n_nodes, a, _ = mention_incidences_synth(n_users, n_users // 2, per_user, seed)
+    rng = np.random.default_rng(seed + 1)
+
+    def names(lead, count):
+        ids = np.arange(count, dtype=np.int64)
+        out = np.full((count, 10), ord(" "), np.uint8)
+        out[:, 1] = ord(lead)
+        out[:, 2:9] = np.stack([_B36[(ids // 36 ** k) % 36] for k in range(6, -1, -1)], 1)
+        return out
+
+    words = names("w", n_words)
+    mentions = np.concatenate([names("u", n_users), names("m", n_nodes - n_users)])
+    mentions[:, 0] = ord("@")
+    upper = mentions.copy()
+    low = (upper >= ord("a")) & (upper <= ord("z"))
+    upper[low] -= 32
+    table = np.concatenate([words, mentions, upper])
+    tok = rng.integers(0, n_words, size=(n_users, per_doc), dtype=np.int64)
+    slots = np.argsort(rng.random((n_users, per_doc)), axis=1)[:, :per_user]
+    spelt = a.astype(np.int64).reshape(n_users, per_user) + n_words
+    spelt += (rng.random(spelt.shape) < 0.2) * n_nodes
+    np.put_along_axis(tok, slots, spelt, axis=1)
+    docs, step = [], 1 << 16
+    for d in range(0, n_users, step):
+        rows = table[tok[d:d + step]].reshape(-1, per_doc * 10)
+        docs.extend(bytes(r).decode("ascii") for r in rows)
+    users = [bytes(r[1:9]).decode("ascii") for r in mentions[:n_users]]
+    cuts = (0, n_users * 9 // 10, n_users * 19 // 20, n_users)
+    return [pd.DataFrame({"text": docs[i:j]}, index=users[i:j]) for i, j in zip(cuts, cuts[1:])]
+
+
+def bench_parse(n_users, dev, reps=3):
+    from graphconvgeo_amd.mentions import (mention_graph_operator, mention_incidences,
+                                           mention_incidences_device)
+    tables = mention_tables_synth(n_users)
+    rec = {"op": "parse", "users": n_users,
+           "text_bytes": int(sum(len(t) + 1 for df in tables for t in df["text"]) - 1)}
+    mention_incidences_device(*[df[:1000] for df in tables], device=dev)   # warm the library
+    t0 = time.perf_counter()
+    want = mention_incidences(*tables)
+    rec.update(host_s=round(time.perf_counter() - t0, 3), nodes=want[1], incidences=int(want[2].size))
+    out, ts = {}, []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out["r"] = mention_incidences_device(*tables, device=dev)
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    got = out["r"]
+    split = {}
+    mention_incidences_device(*tables, device=dev, timings=split)
+    rec.update(device_s=round(float(np.median(ts)), 3), device_all_s=[round(t, 3) for t in ts],
+               device_split_s={k: round(v, 3) for k, v in split.items()},
+               speedup=round(rec["host_s"] / float(np.median(ts)), 2),
+               fallbacks=mention_incidences_device.fallbacks,
+               equal=bool(got[:2] == want[:2] and np.array_equal(got[2].cpu().numpy(), want[2])
+                          and np.array_equal(got[3].cpu().numpy(), want[3])))
+    del got, out, want
+    # the texts to H, either parser
+    ends = {}
+    for parser in ("device", "host", "device"):   # the host parser once: it is the slow one
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        H = mention_graph_operator(*tables, device=dev, parser=parser)
+        torch.cuda.synchronize()
+        ends.setdefault(parser, []).append(time.perf_counter() - t0)
+        ends[parser + "_H"] = H
+    Hh, Hd = ends.pop("host_H"), ends.pop("device_H")
+    rec.update(to_H_host_s=[round(t, 3) for t in ends["host"]],
+               to_H_device_s=[round(t, 3) for t in ends["device"]],
+               to_H_speedup=round(min(ends["host"]) / min(ends["device"]), 2), nnz_H=int(Hd.nnz),
+               H_bitwise=bool(torch.equal(Hh.indptr, Hd.indptr) and torch.equal(Hh.indices, Hd.indices)
+                              and torch.equal(Hh.data.view(torch.int32), Hd.data.view(torch.int32))))
+    emit(rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ops", default="normalize,spgemm,project")
+    ap.add_argument("--parse-users", default="450000,1400000",
+                    help="--ops parse: the sizes of the synthetic user tables")
     ap.add_argument("--configs", default="twitter-us,twitter-world")
     ap.add_argument("--spgemm-cpu-rows", type=int, default=60_000,
                     help="rows of H multiplied on the CPU for the scipy baseline (0 = all)")
@@ -151,6 +247,9 @@ def main():
     if "project" in ops:
         bench_project(20_000, dev, cpu=True)
         bench_project(450_000, dev, cpu=False)
+    if "parse" in ops:
+        for n in args.parse_users.split(","):
+            bench_parse(int(n), dev)
 
 
 if __name__ == "__main__":
