@@ -16,7 +16,13 @@ the most local words from the device (NNModel_loc2lang.local_words), and per pla
 top-ranked words of region_word_scores over the test rows nearest to it, with the recall of the
 place's own words (region_recall).
 
+--nomdn trains the baseline the Gaussian layer is compared against instead, a rectified dense
+layer in place of the Gaussians (NNModel_loc2lang_nomdn): on the raw coordinates, or with --grid
+on their grid representation (grid.grid_representation: l1-normalised sparse rows over a 0.5
+degree grid of the US box, built on the device and never brought to the host).
+
     python examples/loc2lang_pipeline.py [--epochs 40] [--init kmeans --ncomp 6] [--analyses]
+    python examples/loc2lang_pipeline.py --nomdn --grid [--analyses]
 """
 from __future__ import annotations
 
@@ -29,7 +35,7 @@ import scipy.sparse as sps
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from graphconvgeo_amd import geo, kmeans, loc2lang, mdn  # noqa: E402
+from graphconvgeo_amd import geo, grid, kmeans, loc2lang, mdn  # noqa: E402
 
 PLACES = np.array([[40.7, -74.0], [34.0, -118.2], [29.8, -95.4]])
 OWN, COMMON = 10, 10  # words per place, words of everybody
@@ -56,12 +62,25 @@ def main():
     ap.add_argument("--ncomp", type=int, default=6, help="components of --init kmeans")
     ap.add_argument("--analyses", action="store_true",
                     help="also print the device local words and the places' top-ranked words")
+    ap.add_argument("--nomdn", action="store_true",
+                    help="the no-MDN baseline: a rectified dense layer in place of the Gaussians")
+    ap.add_argument("--grid", action="store_true",
+                    help="with --nomdn: the coordinates as sparse rows over a 0.5 degree grid")
     args = ap.parse_args()
+    if args.grid and not args.nomdn:
+        ap.error("--grid is the input of the no-MDN baseline: give --nomdn too")
     rng = np.random.default_rng(0)
     np.random.seed(0)
     (Xtr, Ytr), (Xdev, Ydev), (Xte, Yte) = (synthetic(n, rng) for n in (1200, 300, 300))
 
-    if args.init == "kmeans":
+    # what the model takes for a coordinate array: itself, or its rows over the grid
+    rep = (lambda X: grid.grid_representation(X, device=args.device)) if args.grid else (lambda X: X)
+    if args.nomdn:
+        clf = loc2lang.NNModel_loc2lang_nomdn(n_epochs=args.epochs, batch_size=100, hid_size=32,
+                                              n_gaus_comp=64, early_stopping_max_down=5,
+                                              device=args.device)
+        print("no-MDN baseline on", "the grid representation" if args.grid else "raw coordinates")
+    elif args.init == "kmeans":
         C = args.ncomp
         mus, sigmas, corxy = kmeans.get_cluster_centers(Xtr, C, seed=0, device=args.device)
         print(f"k-means -> {C} Gaussians")
@@ -71,25 +90,27 @@ def main():
         mus, sigmas, corxy = mdn.cluster_params(Xtr, labels, C, raw=True)
         print(f"{C} regions -> {C} Gaussians")
 
-    clf = loc2lang.NNModel_loc2lang(n_epochs=args.epochs, batch_size=100, hid_size=32,
-                                    n_gaus_comp=C, mus=mus, sigmas=sigmas, corxy=corxy,
-                                    early_stopping_max_down=5, device=args.device)
-    ppl_test, ppl_dev = clf.fit(Xtr, Ytr, Xdev, Ydev, Xte, Yte)
+    if not args.nomdn:
+        clf = loc2lang.NNModel_loc2lang(n_epochs=args.epochs, batch_size=100, hid_size=32,
+                                        n_gaus_comp=C, mus=mus, sigmas=sigmas, corxy=corxy,
+                                        early_stopping_max_down=5, device=args.device)
+    Xte_in = rep(Xte)
+    ppl_test, ppl_dev = clf.fit(rep(Xtr), Ytr, rep(Xdev), Ydev, Xte_in, Yte)
     first, last = clf.history[0], clf.history[-1]
     print(f"dev loss {first['val_loss']:.3f} -> {last['val_loss']:.3f} in {len(clf.history)} epochs; "
           f"perplexity dev {ppl_dev:.2f}, test {ppl_test:.2f}")
 
     lat, lon = np.meshgrid(np.linspace(27, 43, 17), np.linspace(-121, -71, 26), indexing="ij")
-    grid = np.stack([lat.ravel(), lon.ravel()], axis=1).astype(np.float32)
-    words = loc2lang.local_words(clf.predict(grid), k=12)
+    mesh = rep(np.stack([lat.ravel(), lon.ravel()], axis=1).astype(np.float32))
+    words = loc2lang.local_words(clf.predict(mesh), k=12)
     local = int((words < OWN * len(PLACES)).sum())
     print("most local words:", words.tolist(), f"({local} of 12 belong to one place)")
     if args.analyses:
-        print("most local words, on the device:", clf.local_words(grid, k=12).tolist())
+        print("most local words, on the device:", clf.local_words(mesh, k=12).tolist())
         nearest = np.abs(Xte[:, None, :] - PLACES[None]).sum(axis=-1).argmin(axis=1)
         group_rows = np.argsort(nearest, kind="stable")
         group_ptr = np.concatenate([[0], np.cumsum(np.bincount(nearest, minlength=len(PLACES)))])
-        scores = clf.region_word_scores(Xte, group_ptr, group_rows)
+        scores = clf.region_word_scores(Xte_in, group_ptr, group_rows)
         gold_ptr = OWN * np.arange(len(PLACES) + 1)
         rec = loc2lang.region_recall(scores, gold_ptr, np.arange(OWN * len(PLACES)),
                                      fractions=(0.1, 0.25))

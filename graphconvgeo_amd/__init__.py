@@ -27,9 +27,12 @@ Product modules (all compute runs in libgcg_spmm.so HIP kernels; no CPU fallback
   tfidf        DataLoader.tfidf (data.py:378-397): tokenising on the host or, opt-in, on the GPU
                (tokenize_corpus_device), counting, document frequencies, pruning and tf-idf
                weighting on the GPU, dataloader_features
+  grid         grid_representation (loc2lang.py:298-322): coordinates as l1-normalised sparse rows
+               over a lat/lon grid, the input of loc2lang's no-MDN baseline
   synth        seeded synthetic graphs / features for the BASELINE configs
 
-`MLP`, `input_convolution`, `NNModel_lang2loc`, `NNModel_lang2locshared`, `NNModel_loc2lang` and
+`MLP`, `input_convolution`, `NNModel_lang2loc`, `NNModel_lang2locshared`, `NNModel_loc2lang`,
+`NNModel_loc2lang_nomdn`, `grid_representation`, `LatLonGrid`, `US_BBOX`, `WORLD_BBOX` and
 `DeviceCSR` are imported lazily from the package itself.
 """
 import os as _os
@@ -46,12 +49,15 @@ _os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "8")
 
 __all__ = ["sparse", "ops", "layers", "dense", "distributed", "dist_train", "graph", "mentions",
            "training", "mlpconv", "mlp", "geo", "mdn", "loc2lang", "dialect", "tfidf",
-           "synth", "MLP",
+           "grid", "synth", "MLP", "NNModel_loc2lang_nomdn", "grid_representation", "LatLonGrid",
+           "US_BBOX", "WORLD_BBOX",
            "input_convolution",
            "NNModel_lang2loc", "NNModel_lang2locshared", "NNModel_loc2lang", "DeviceCSR"]
 
 _LAZY = {"MLP": "mlp", "input_convolution": "mlp", "NNModel_lang2loc": "mdn",
-         "NNModel_lang2locshared": "mdn", "NNModel_loc2lang": "loc2lang", "DeviceCSR": "sparse"}
+         "NNModel_lang2locshared": "mdn", "NNModel_loc2lang": "loc2lang", "DeviceCSR": "sparse",
+         "NNModel_loc2lang_nomdn": "loc2lang", "grid_representation": "grid", "LatLonGrid": "grid",
+         "US_BBOX": "grid", "WORLD_BBOX": "grid"}
 
 
 def __getattr__(name):

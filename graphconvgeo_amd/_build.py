@@ -16,7 +16,8 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 # conversion, CSR utilities, graph build, SpGEMM, the MFMA dense side in four files over
 # dense_shared.h (plain and f32-fused GEMM; NT GEMM; the bf16x6 fused output layer + softmax/xent
 # rows; split-K TN), Philox dropout, the mini-batch MLP's epoch segmentation and W1 step,
-# k-d-tree labels + geolocation metrics, the mixture-density location head with the Gaussian layer of the inverse model, the softmax cross-entropy against sparse
+# k-d-tree labels + geolocation metrics, the grid representation of loc2lang's no-MDN baseline,
+# the mixture-density location head with the Gaussian layer of the inverse model, the softmax cross-entropy against sparse
 # soft targets, the k-means initialisation of the Gaussian components, the dialect-embedding
 # evaluation (scaling, neighbour ranks, kneighbors), the row log-sum-exp and per-word column sums
 # of the location-to-language model's analyses, the TF-IDF features over token ids (counting,
@@ -27,14 +28,15 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in
            ("spmm.hip", "spmm_bf16.hip", "csr_ops.hip", "graph_build.hip", "spgemm.hip",
             "dense_gemm.hip", "dense_nt.hip", "dense_fused.hip", "dense_tn.hip", "dropout.hip",
-            "minibatch.hip", "geo.hip", "kmeans.hip", "mdn.hip", "softmax_csr.hip", "neighbours.hip",
+            "minibatch.hip", "geo.hip", "grid.hip", "kmeans.hip", "mdn.hip", "softmax_csr.hip", "neighbours.hip",
             "vocab_stats.hip", "tfidf.hip", "tokenize.hip", "errors.cpp")]
 INTERNAL_HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "layout.h", "scratch.h",
                                                     "spmm_shared.h", "dense_shared.h",
                                                     "index_kernels.h",
                                                     "gemm_epilogue.inc", "philox.h",
                                                     "rectify_backward_pass.inc",
-                                                    "segment_kernels.h", "row_maxsum.h")]
+                                                    "segment_kernels.h", "row_maxsum.h",
+                                                    "haversine.h")]
 HEADER = os.path.join(REPO_DIR, "include", "gcg_spmm.h")
 LIB = os.path.join(PKG_DIR, "libgcg_spmm.so")
 ARCH = os.environ.get("GCG_OFFLOAD_ARCH", "gfx950")

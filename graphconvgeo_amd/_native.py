@@ -76,6 +76,9 @@ SIGNATURES = {
     "gcg_minibatch_w1_step_f32": (C.c_int, [_i64, _i64, _p, _p, _p, _p, _i64, _i64, _p, _p, _p,
                                             _p, _p, C.c_float, C.c_float, _p, C.c_float,
                                             C.c_float, C.c_float, _p]),
+    "gcg_minibatch_w1_adamax_step_f32": (C.c_int, [_i64, _i64, _p, _p, _p, _p, _i64, _i64, _p, _p,
+                                                   _p, _p, _p, _p, C.c_float, C.c_float,
+                                                   C.c_float, _p]),
     "gcg_minibatch_segment_dropout": (C.c_int, [_i64, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p,
                                                 _p, _p, _p, _p, _p, _p, C.c_size_t, C.c_uint32,
                                                 C.c_float, C.c_uint64, _p, C.c_uint32, _p]),
@@ -163,6 +166,12 @@ SIGNATURES = {
     "gcg_nearest_class_f64": (C.c_int, [_i64, _p, _i64, _p, C.c_double, _p, _p, _p]),
     "gcg_geo_eval_f64": (C.c_int, [_i64, _p, C.c_int, _p, _i64, _p, C.c_double, C.c_double, _p,
                                    _p, _p, _p]),
+    # the grid representation of loc2lang's no-MDN baseline (csrc/grid.hip)
+    "gcg_grid_count_f64_workspace_bytes": (C.c_int, [_i64, _psz]),
+    "gcg_grid_count_f64": (C.c_int, [_i64, _p, _i64, _p, _i64, _p, C.c_double, C.c_double, C.c_int,
+                                     _p, _p, _p, _p, C.c_size_t, _p]),
+    "gcg_grid_fill_f64": (C.c_int, [_i64, _p, _i64, _p, _i64, _p, C.c_double, C.c_double, C.c_int,
+                                    _p, _p, _i64, _p, _p, _p]),
     # k-means initialisation of the Gaussian components (csrc/kmeans.hip)
     "gcg_kmeans_centre_tile": (C.c_int32, []),
     "gcg_kmeans_assign_f64_workspace_bytes": (C.c_int, [_i64, _psz]),

@@ -13,6 +13,7 @@
 
 #include <cmath>
 
+#include "haversine.h"
 #include "scratch.h"
 #include "segment_kernels.h"
 
@@ -20,7 +21,6 @@ using namespace gcg;
 
 namespace {
 
-constexpr double kDegToRad = 3.14159265358979323846 / 180.0;
 // medians staged per LDS tile of nearest_class_kernel: 3 doubles each, 48 KiB, so two
 // workgroups still share a CU's LDS
 constexpr int kClassTile = 2048;
@@ -212,15 +212,7 @@ __global__ void gather_labels_kernel(int64_t N, int64_t C, const int32_t* __rest
   }
 }
 
-// The haversine package's distance between points given in radians; `a` is clamped to 1 so
-// that rounding at antipodal points cannot produce a NaN.
-__device__ __forceinline__ double haversine_rad(double lat1, double cos1, double lng1, double lat2,
-                                                double cos2, double lng2, double two_r) {
-  const double sa = sin((lat2 - lat1) * 0.5), so = sin((lng2 - lng1) * 0.5);
-  const double a = sa * sa + cos1 * cos2 * (so * so);
-  return two_r * asin(sqrt(fmin(a, 1.0)));
-}
-
+// (haversine_rad, the distance itself: haversine.h)
 __global__ void haversine_kernel(int64_t M, const double* __restrict__ A,
                                  const double* __restrict__ B, double two_r,
                                  double* __restrict__ out) {

@@ -1,7 +1,8 @@
 // minibatch.hip -- the mini-batch MLP trainer's own kernels (reference mlp.py:96-311, driven by
 // tensormain.main_justinputconv): the column grouping of every batch of an epoch at once, and
 // the one-pass update of the sparse-input weight W1 (data gradient of the batch's touched rows,
-// L1/L2 penalty gradient and Lasagne Adam in a single sweep over W1, m, v).
+// L1/L2 penalty gradient and Lasagne Adam in a single sweep over W1, m, v; or, for loc2lang's
+// no-MDN baseline, the data gradient and Lasagne Adamax: the same kernel on another rule).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -237,20 +238,42 @@ gcg_status seg_space(const char* fn, int64_t n_sel, int64_t batch, int64_t F, in
 // within noise at 64 nonzeros per row, 8 a little ahead at ~700 (profiles/mlp/w1_variants.jsonl).
 constexpr int kStepRows = 8;
 
-// One element of the step: the gradient g = d + (l1 sgn(w) + 2 l2 w) in l1l2_grad_kernel's
-// expression, then adam_kernel's update (csr_ops.hip), bit for bit.
-__device__ __forceinline__ void step_element(float& p, float& m, float& v, float d, float c1,
-                                             float c2, float a_t, float b1, float b2, float ca,
-                                             float cb, float eps) {
-  const float x = p;
-  const float sg = x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f);
-  const float gi = d + (c1 * sg + c2 * x);
-  const float mi = b1 * m + ca * gi;
-  const float vi = b2 * v + cb * gi * gi;
-  m = mi;
-  v = vi;
-  p = x - (a_t * mi) / (sqrtf(vi) + eps);
-}
+// The update rule of the step, one element at a time. Both take the data gradient d and the
+// element's parameter and two state values; a rule's constants are computed once per thread.
+//
+// Adam: the gradient g = d + (l1 sgn(w) + 2 l2 w) in l1l2_grad_kernel's expression, then
+// adam_kernel's update (csr_ops.hip), bit for bit.
+struct AdamRule {
+  float c1, c2, a_t, b1, b2, ca, cb, eps;
+  __device__ AdamRule(float l1, float l2, float a_t_, float b1_, float b2_, float eps_)
+      : c1(l1), c2(2.0f * l2), a_t(a_t_), b1(b1_), b2(b2_), ca(1.0f - b1_), cb(1.0f - b2_),
+        eps(eps_) {}
+  __device__ __forceinline__ void operator()(float& p, float& m, float& v, float d) const {
+    const float x = p;
+    const float sg = x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f);
+    const float gi = d + (c1 * sg + c2 * x);
+    const float mi = b1 * m + ca * gi;
+    const float vi = b2 * v + cb * gi * gi;
+    m = mi;
+    v = vi;
+    p = x - (a_t * mi) / (sqrtf(vi) + eps);
+  }
+};
+
+// Adamax without a penalty (loc2lang's build has none): g = d, then adamax_kernel's update
+// (csr_ops.hip), bit for bit; the second state is u.
+struct AdamaxRule {
+  float a_t, b1, b2, ca, eps;
+  __device__ AdamaxRule(float, float, float a_t_, float b1_, float b2_, float eps_)
+      : a_t(a_t_), b1(b1_), b2(b2_), ca(1.0f - b1_), eps(eps_) {}
+  __device__ __forceinline__ void operator()(float& p, float& m, float& u, float d) const {
+    const float mi = b1 * m + ca * d;
+    const float ui = fmaxf(b2 * u, fabsf(d));
+    m = mi;
+    u = ui;
+    p = p - (a_t * mi) / (ui + eps);
+  }
+};
 
 // A workgroup owns kStepRows consecutive rows of W1. Its segment candidates are the (at most
 // kStepRows) segments of this batch whose column falls into those rows: a 64-ary search for the
@@ -263,7 +286,7 @@ __device__ __forceinline__ void step_element(float& p, float& m, float& v, float
 // A segment is never split across waves: its sum keeps the entries' order, which is what makes
 // the step bitwise the composed kernels' and reproducible. W, m, v are requested before the
 // gather and used after it. Lanes past K gather column 0 (in bounds, unused).
-template <int VEC>
+template <int VEC, typename Rule>
 __global__ __launch_bounds__(kBlock) void w1_step_kernel(
     int64_t F, int K, float* __restrict__ P, float* __restrict__ M, float* __restrict__ V,
     const float* __restrict__ G, int64_t ldg, const int32_t* __restrict__ seg_range,
@@ -290,9 +313,7 @@ __global__ __launch_bounds__(kBlock) void w1_step_kernel(
     }
   }
   const int cand = (lane < kStepRows && lo + lane < se) ? seg_col[lo + lane] : -1;
-  const float a_t = *step_dev;
-  const float c1 = l1, c2 = 2.0f * l2;
-  const float ca = 1.0f - b1, cb = 1.0f - b2;
+  const Rule step_element(l1, l2, *step_dev, b1, b2, eps);
   const int chunks = (K + kWave * VEC - 1) / (kWave * VEC);
   for (int t = w; t < nr * chunks; t += kWavesPerBlock) {
     const int i = t / chunks, ch = t - i * chunks;
@@ -322,10 +343,10 @@ __global__ __launch_bounds__(kBlock) void w1_step_kernel(
         d.x = d.x + a * g.x; d.y = d.y + a * g.y; d.z = d.z + a * g.z; d.w = d.w + a * g.w;
       }
       if (on) {
-        step_element(p.x, m.x, v.x, d.x, c1, c2, a_t, b1, b2, ca, cb, eps);
-        step_element(p.y, m.y, v.y, d.y, c1, c2, a_t, b1, b2, ca, cb, eps);
-        step_element(p.z, m.z, v.z, d.z, c1, c2, a_t, b1, b2, ca, cb, eps);
-        step_element(p.w, m.w, v.w, d.w, c1, c2, a_t, b1, b2, ca, cb, eps);
+        step_element(p.x, m.x, v.x, d.x);
+        step_element(p.y, m.y, v.y, d.y);
+        step_element(p.z, m.z, v.z, d.z);
+        step_element(p.w, m.w, v.w, d.w);
         *reinterpret_cast<float4*>(M + o) = m;
         *reinterpret_cast<float4*>(V + o) = v;
         *reinterpret_cast<float4*>(P + o) = p;
@@ -341,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void w1_step_kernel(
       for (int j = s; j < e; ++j)
         d = d + ent_val[j] * gcol[static_cast<int64_t>(ent_pos[j]) * ldg];
       if (on) {
-        step_element(p, m, v, d, c1, c2, a_t, b1, b2, ca, cb, eps);
+        step_element(p, m, v, d);
         M[o] = m;
         V[o] = v;
         P[o] = p;
@@ -417,6 +438,41 @@ gcg_status segment_impl(const char* fn, int64_t n_rows, int64_t n_cols, const in
   return GCG_OK;
 }
 
+// Both W1 steps: the checks and the launch, the kernel instantiated on the update rule.
+template <typename Rule>
+gcg_status w1_step_impl(const char* fn, int64_t F, int64_t K, float* W, float* m, float* v,
+                        const float* G, int64_t ldg, int64_t batch, const int32_t* seg_range,
+                        const int32_t* seg_col, const int32_t* seg_ptr, const int32_t* ent_pos,
+                        const float* ent_val, float l1, float l2, const float* step_dev,
+                        float beta1, float beta2, float eps, gcg_stream_t stream) {
+  if (F < 0 || K < 0 || batch < 0 || F > INT32_MAX || K > INT32_MAX || ldg < K)
+    return fail(GCG_ERR_INVALID_ARG, "%s: bad sizes F=%lld K=%lld batch=%lld ldg=%lld", fn,
+                static_cast<long long>(F), static_cast<long long>(K),
+                static_cast<long long>(batch), static_cast<long long>(ldg));
+  if (F == 0 || K == 0) return GCG_OK;
+  if (W == nullptr || m == nullptr || v == nullptr || seg_range == nullptr || seg_col == nullptr ||
+      seg_ptr == nullptr || step_dev == nullptr ||
+      (batch > 0 && (G == nullptr || ent_pos == nullptr || ent_val == nullptr)))
+    return fail(GCG_ERR_INVALID_ARG, "%s: NULL operand", fn);
+  if (!aligned(W, 4) || !aligned(m, 4) || !aligned(v, 4) || !aligned(G, 4) ||
+      !aligned(seg_range, 4) || !aligned(step_dev, 4))
+    return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B aligned", fn);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(static_cast<unsigned>((F + kStepRows - 1) / kStepRows));
+  const bool vec = K % 4 == 0 && ldg % 4 == 0 && aligned(G, 16) && aligned(W, 16) &&
+                   aligned(m, 16) && aligned(v, 16);
+  if (vec)
+    hipLaunchKernelGGL((w1_step_kernel<4, Rule>), grid, dim3(kBlock), 0, st, F, static_cast<int>(K),
+                       W, m, v, G, ldg, seg_range, seg_col, seg_ptr, ent_pos, ent_val, l1, l2,
+                       step_dev, beta1, beta2, eps);
+  else
+    hipLaunchKernelGGL((w1_step_kernel<1, Rule>), grid, dim3(kBlock), 0, st, F, static_cast<int>(K),
+                       W, m, v, G, ldg, seg_range, seg_col, seg_ptr, ent_pos, ent_val, l1, l2,
+                       step_dev, beta1, beta2, eps);
+  GCG_HIP_CHECK(hipGetLastError());
+  return GCG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -473,33 +529,21 @@ gcg_status gcg_minibatch_w1_step_f32(int64_t F, int64_t K, float* W, float* m, f
                                      const float* ent_val, float l1, float l2,
                                      const float* step_dev, float beta1, float beta2, float eps,
                                      gcg_stream_t stream) {
-  const char* fn = "gcg_minibatch_w1_step_f32";
-  if (F < 0 || K < 0 || batch < 0 || F > INT32_MAX || K > INT32_MAX || ldg < K)
-    return fail(GCG_ERR_INVALID_ARG, "%s: bad sizes F=%lld K=%lld batch=%lld ldg=%lld", fn,
-                static_cast<long long>(F), static_cast<long long>(K),
-                static_cast<long long>(batch), static_cast<long long>(ldg));
-  if (F == 0 || K == 0) return GCG_OK;
-  if (W == nullptr || m == nullptr || v == nullptr || seg_range == nullptr || seg_col == nullptr ||
-      seg_ptr == nullptr || step_dev == nullptr ||
-      (batch > 0 && (G == nullptr || ent_pos == nullptr || ent_val == nullptr)))
-    return fail(GCG_ERR_INVALID_ARG, "%s: NULL operand", fn);
-  if (!aligned(W, 4) || !aligned(m, 4) || !aligned(v, 4) || !aligned(G, 4) ||
-      !aligned(seg_range, 4) || !aligned(step_dev, 4))
-    return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B aligned", fn);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid(static_cast<unsigned>((F + kStepRows - 1) / kStepRows));
-  const bool vec = K % 4 == 0 && ldg % 4 == 0 && aligned(G, 16) && aligned(W, 16) &&
-                   aligned(m, 16) && aligned(v, 16);
-  if (vec)
-    hipLaunchKernelGGL((w1_step_kernel<4>), grid, dim3(kBlock), 0, st, F, static_cast<int>(K), W, m,
-                       v, G, ldg, seg_range, seg_col, seg_ptr, ent_pos, ent_val, l1, l2, step_dev,
-                       beta1, beta2, eps);
-  else
-    hipLaunchKernelGGL((w1_step_kernel<1>), grid, dim3(kBlock), 0, st, F, static_cast<int>(K), W, m,
-                       v, G, ldg, seg_range, seg_col, seg_ptr, ent_pos, ent_val, l1, l2, step_dev,
-                       beta1, beta2, eps);
-  GCG_HIP_CHECK(hipGetLastError());
-  return GCG_OK;
+  return w1_step_impl<AdamRule>("gcg_minibatch_w1_step_f32", F, K, W, m, v, G, ldg, batch,
+                                seg_range, seg_col, seg_ptr, ent_pos, ent_val, l1, l2, step_dev,
+                                beta1, beta2, eps, stream);
+}
+
+gcg_status gcg_minibatch_w1_adamax_step_f32(int64_t F, int64_t K, float* W, float* m, float* u,
+                                            const float* G, int64_t ldg, int64_t batch,
+                                            const int32_t* seg_range, const int32_t* seg_col,
+                                            const int32_t* seg_ptr, const int32_t* ent_pos,
+                                            const float* ent_val, const float* step_dev,
+                                            float beta1, float beta2, float eps,
+                                            gcg_stream_t stream) {
+  return w1_step_impl<AdamaxRule>("gcg_minibatch_w1_adamax_step_f32", F, K, W, m, u, G, ldg, batch,
+                                  seg_range, seg_col, seg_ptr, ent_pos, ent_val, 0.f, 0.f,
+                                  step_dev, beta1, beta2, eps, stream);
 }
 
 }  // extern "C"

@@ -15,6 +15,9 @@ l1-normalised bag of words by categorical cross-entropy with Adamax (loc2lang.py
   LasagneAdamax            lasagne.updates.adamax, one launch per       gcg_adamax_step_f32
                            parameter
   NNModel_loc2lang         the reference's class: constructor arguments, fit, predict
+  NNModel_loc2lang_nomdn   its nomdn=True build, the baseline: a rectified dense  gcg_minibatch_w1_adamax_step_f32
+                           layer in place of the Gaussians, over the grid
+                           representation (grid.py, sparse) or raw coordinates
   local_words              get_local_words (loc2lang.py:755-766) without the named-entity filter
   row_lse                  the float64 log-sum-exp of every logits row  gcg_row_lse_f64
   softmax_column_stats     per word, sum_n p and sum_n p log p of       gcg_softmax_column_stats_f64
@@ -44,6 +47,7 @@ from . import sparse as gs
 from ._native import call, device_scalar, workspace, workspace_bytes
 from .layers import _as_tensor, _glorot_uniform
 from .mdn import MAX_COMPONENTS, _check_components, split_dparams
+from .mlp import BatchSegments, plan_segmented_epoch, w1_adamax_step
 from .sparse import _ld, _ptr, _stream_handle
 from .training import (LasagneOptimizer, MiniBatchTrainer, lower_loss_by_margin, n_batches,
                        run_epochs)
@@ -55,6 +59,11 @@ MAX_HIDDEN = 1024           # the rectify backward's one-pass kernel (sparse.rel
 EVAL_CHUNK_BYTES = 1 << 30  # a chunk's logits stay under this in evaluation and predict
 
 RegionRecall = namedtuple("RegionRecall", "ks recall oracle per_group ranks")
+
+
+def _row_chunk(x, a: int, b: int):
+    """Rows [a, b) of a model input: a slice of a dense tensor, DeviceCSR.row_slice of a sparse one."""
+    return x.row_slice(a, b) if isinstance(x, gs.DeviceCSR) else x[a:b]
 
 
 # -- the Gaussian layer ---------------------------------------------------------------------
@@ -453,27 +462,19 @@ class NNModel_loc2lang(MiniBatchTrainer):
                  early_stopping_max_down=10, dtype="float32", autoencoder=100, reload=False,
                  n_gaus_comp=500, mus=None, sigmas=None, corxy=None, nomdn=False,
                  dataset_name="", init_parameters=None, device="cuda"):
-        if nomdn:
-            raise NotImplementedError("nomdn (a rectified dense layer in place of the Gaussians) "
-                                      "is not built")
+        input_size = self._check_mode(nomdn, input_size)
         if reload:
             raise NotImplementedError("reload (a pickled model file) is not built")
         if dtype != "float32":
             raise ValueError("the GPU path computes in float32 (loc2lang.py dtype='float32')")
-        if input_size is not None and int(input_size) != 2:
-            raise NotImplementedError("the input is a coordinate [lat, lon] (input_size 2); the "
-                                      "grid representation is not built")
-        if not 1 <= int(n_gaus_comp) <= MAX_COMPONENTS:
-            raise ValueError(f"n_gaus_comp must be in [1, {MAX_COMPONENTS}]")
+        if not 1 <= int(n_gaus_comp) <= self.max_units:
+            raise ValueError(f"n_gaus_comp must be in [1, {self.max_units}]")
         if not 0 <= int(hid_size) <= MAX_HIDDEN:
             raise ValueError(f"hid_size must be in [0, {MAX_HIDDEN}]")
         if int(batch_size) < 1:
             raise ValueError("batch_size must be positive")
         C = int(n_gaus_comp)
-        for x, shape, name in ((mus, (C, 2), "mus"), (sigmas, (C, 2), "sigmas"),
-                               (corxy, (C,), "corxy")):
-            if x is not None and np.shape(x) != shape:
-                raise ValueError(f"{name} must have shape {shape}, got {np.shape(x)}")
+        self._check_component_args(C, mus, sigmas, corxy)
         self.n_epochs = n_epochs
         self.batch_size = int(batch_size)
         self.regul_coef = regul_coef
@@ -482,20 +483,49 @@ class NNModel_loc2lang(MiniBatchTrainer):
         self.dropout_coef = dropout_coef
         self.early_stopping_max_down = early_stopping_max_down
         self.dtype = dtype
-        self.input_size = 2
+        self.input_size = input_size
         self.output_size = None if output_size is None else int(output_size)
         self.autoencoder = autoencoder
         self.reload = False
         self.n_gaus_comp = C
         self.mus_init, self.sigmas_init, self.corxy_init = mus, sigmas, corxy
-        self.nomdn = False
+        self.nomdn = type(self).nomdn
         self.dataset_name = dataset_name
         self.init_parameters = init_parameters
         self.device = torch.device(device)
         self.history = []
         self.params = None
-        if self.output_size is not None:  # the reference builds in its constructor
-            self._build(self.output_size)
+        if self.output_size is not None and self.input_size is not None:
+            self._build(self.output_size)  # the reference builds in its constructor
+
+    # -- what the no-MDN baseline (NNModel_loc2lang_nomdn) states differently ---------------
+    nomdn = False
+    max_units = MAX_COMPONENTS  # the first layer's widest
+
+    def _check_mode(self, nomdn, input_size) -> Optional[int]:
+        """The constructor's refusals that depend on the input mode; returns input_size."""
+        if nomdn:
+            raise NotImplementedError("nomdn (a rectified dense layer in place of the Gaussians) "
+                                      "is a class of its own: NNModel_loc2lang_nomdn")
+        if input_size is not None and int(input_size) != 2:
+            raise NotImplementedError("the input is a coordinate [lat, lon] (input_size 2); the "
+                                      "grid representation is NNModel_loc2lang_nomdn's input")
+        return 2
+
+    @staticmethod
+    def _check_component_args(C, mus, sigmas, corxy) -> None:
+        for x, shape, name in ((mus, (C, 2), "mus"), (sigmas, (C, 2), "sigmas"),
+                               (corxy, (C,), "corxy")):
+            if x is not None and np.shape(x) != shape:
+                raise ValueError(f"{name} must have shape {shape}, got {np.shape(x)}")
+
+    def _first_layer(self, x) -> torch.Tensor:
+        """The first layer's output [n, n_gaus_comp] (the reference's f_gaus)."""
+        return bigaus_forward(x, self.mus, self.sigmas, self.corxy)
+
+    def _set_train(self, x) -> None:
+        """fit's training input, as _prepare_epoch gathers it per epoch."""
+        self._train_data = x
 
     # -- model --------------------------------------------------------------------------
     @property
@@ -528,8 +558,8 @@ class NNModel_loc2lang(MiniBatchTrainer):
                                        epsilon=1e-8)
 
     def _features(self, x: torch.Tensor):
-        """(G, H): the Gaussian layer's output and the last layer before the projection."""
-        G = bigaus_forward(x, self.mus, self.sigmas, self.corxy)
+        """(G, H): the first layer's output and the last layer before the projection."""
+        G = self._first_layer(x)
         if not self.hid_size:
             return G, G
         return G, dense.gemm_nt(G, self._proj_h.fwd.get(self.Wh, True), bias=self.bh, act="relu")
@@ -544,7 +574,7 @@ class NNModel_loc2lang(MiniBatchTrainer):
     def _to_coords(self, X, name: str = "X") -> torch.Tensor:
         if sps.issparse(X) or isinstance(X, gs.DeviceCSR):
             raise NotImplementedError("the input is a dense [n, 2] coordinate array; the sparse "
-                                      "grid representation is not built")
+                                      "grid representation is NNModel_loc2lang_nomdn's input")
         if isinstance(X, torch.Tensor):
             X = X.detach().cpu().numpy()
         X = np.asarray(X)
@@ -561,8 +591,8 @@ class NNModel_loc2lang(MiniBatchTrainer):
         losses = torch.empty(n, dtype=torch.float32, device=self.device)
         for a in range(0, n, step):
             b = min(a + step, n)
-            losses[a:b] = xent_csr_forward_backward(self._logits(x[a:b]), Y, rows_all[a:b],
-                                                    want_grad=False)[0]
+            Z = self._logits(_row_chunk(x, a, b))
+            losses[a:b] = xent_csr_forward_backward(Z, Y, rows_all[a:b], want_grad=False)[0]
         return float(np.cumsum(losses.cpu().numpy().astype(np.float64))[-1] / n)
 
     # -- training -----------------------------------------------------------------------
@@ -618,8 +648,9 @@ class NNModel_loc2lang(MiniBatchTrainer):
         words, scipy sparse or dense [n, V], uploaded once as CSR. Returns
         (perplexity_test, perplexity_dev). epoch_orders (tests, measurement): one permutation of
         the training rows per epoch instead of the np.random.shuffle draws."""
-        self._train_data, self._y_train = self._split(X_train, Y_train, "train")
-        self._n_train = self._train_data.shape[0]
+        x_train, self._y_train = self._split(X_train, Y_train, "train")
+        self._set_train(x_train)
+        self._n_train = x_train.shape[0]
         x_dev, y_dev = self._split(X_dev, Y_dev, "dev")
         x_test, y_test = self._split(X_test, Y_test, "test")
         V = self._y_train.n_cols
@@ -665,7 +696,7 @@ class NNModel_loc2lang(MiniBatchTrainer):
         n, step = x.shape[0], self._chunk_rows()
         out = np.empty((n, self.output_size), np.float32)
         for a in range(0, n, step):
-            Z = self._logits(x[a:a + step])
+            Z = self._logits(_row_chunk(x, a, min(a + step, n)))
             out[a:a + step] = softmax_wide(Z, out=Z).cpu().numpy()
         return out
 
@@ -673,7 +704,7 @@ class NNModel_loc2lang(MiniBatchTrainer):
     def gaus_output(self, X) -> np.ndarray:
         """f_gaus (loc2lang.py:208): the Gaussian layer's output [n, n_gaus_comp]."""
         self._built()
-        return bigaus_forward(self._to_coords(X), self.mus, self.sigmas, self.corxy).cpu().numpy()
+        return self._first_layer(self._to_coords(X)).cpu().numpy()
 
     # -- the analyses (loc2lang.py:516-614, 693-766) ------------------------------------------------
     def _scan(self, x: torch.Tensor, per_chunk) -> None:
@@ -683,7 +714,7 @@ class NNModel_loc2lang(MiniBatchTrainer):
         n, step = x.shape[0], self._chunk_rows()
         for a in range(0, n, step):
             b = min(a + step, n)
-            Z = self._logits(x[a:b])
+            Z = self._logits(_row_chunk(x, a, b))
             per_chunk(a, b, Z, row_lse(Z))
 
     @torch.no_grad()
@@ -788,6 +819,196 @@ class NNModel_loc2lang(MiniBatchTrainer):
         with torch.no_grad():
             for p, v in zip(self.params, params):
                 p.copy_(_as_tensor(v, tuple(p.shape), self.device))
+
+
+class NNModel_loc2lang_nomdn(NNModel_loc2lang):
+    """The baseline the Gaussian layer is compared against: loc2lang.NNModel with nomdn=True
+    (loc2lang.py:167-171), a rectified dense layer of n_gaus_comp units (the reference keeps that
+    name) where the Gaussians were. Everything else is NNModel_loc2lang's: the epoch loop, the
+    selection rule, the loss, the chunked evaluation, predict and the analyses.
+
+    Network: G = rectify(X.Wg + bg); relu(G.Wh + bh) when hid_size is non-zero; the projection to
+    output_size logits. The parameter list is [Wg, bg, (Wh, bh,) Wo, bo] (get_params, set_params,
+    init_parameters, names); GlorotUniform weights drawn in Lasagne's construction order Wg, Wh, Wo
+    on NumPy's global stream, zero biases. Adamax, lr 2e-3, on every parameter.
+
+    Input. Sparse -- a scipy CSR or a DeviceCSR, input_size = its width: the grid representation
+    (grid.grid_representation), the reference's `-nomdn` with a grid. Or a dense [n, input_size]
+    array: the reference's `-nomdn` on raw coordinates, input_size 2. input_size=None takes the
+    width at fit. fit, predict, gaus_output and every analysis take either kind (a sparse input
+    goes through in row chunks, DeviceCSR.row_slice); a width other than the model's is a
+    ValueError.
+
+    The sparse epoch is mlp.MLP's: the epoch's batches are segmented by column on the device
+    (mlp.BatchSegments, one per run of plan_segmented_epoch), the forward of a batch is
+    spmm_rows(X, Wg, bg, rows, act="relu"), and the step runs the rectify backward with its
+    column sums for bg, then Wg's whole update in one pass over Wg, m, u
+    (gcg_minibatch_w1_adamax_step_f32: no input_size x n_gaus_comp gradient exists; a row of Wg
+    that no training row touches keeps its bits), then one Adamax launch for each other
+    parameter, on the same step count. No host synchronisation between an epoch's first and
+    last batch.
+
+    With a dense input the first layer and its gradients are plain torch ops (addmm, relu, the
+    transposed product): the inner dimension is the input's width, 2, and nothing there is hot.
+
+    mus, sigmas and corxy are accepted and unused, as the reference's nomdn build ignores them;
+    reload and a dtype other than float32 are refused as in NNModel_loc2lang. Left out: another
+    first-layer activation (the reference's log line says tanh, its code rectifies)."""
+
+    nomdn = True
+    max_units = MAX_HIDDEN  # the first layer is rectified: the rectify backward's one-pass kernel
+
+    def __init__(self, *args, **kw):
+        self._inputs = {}   # MiniBatchTrainer._input's upload cache
+        self._sparse = False
+        super().__init__(*args, **kw)
+
+    def _check_mode(self, nomdn, input_size) -> Optional[int]:
+        if input_size is None:
+            return None
+        if int(input_size) < 1:
+            raise ValueError("input_size must be positive")
+        self.in_size = int(input_size)  # what MiniBatchTrainer._input checks a sparse X against
+        return self.in_size
+
+    @staticmethod
+    def _check_component_args(C, mus, sigmas, corxy) -> None:
+        pass
+
+    @property
+    def names(self):
+        return ["Wg", "bg"] + (["Wh", "bh"] if self.hid_size else []) + ["Wo", "bo"]
+
+    def _build(self, V: int):
+        if not 1 <= V <= MAX_COLS:
+            raise ValueError(f"output_size must be in [1, {MAX_COLS}]")
+        F, C, K = self.input_size, self.n_gaus_comp, self.hid_size
+        init = self.init_parameters
+        if init is not None:
+            if len(init) != len(self.names):
+                raise ValueError(f"init_parameters must be [{', '.join(self.names)}], as "
+                                 "lasagne.layers.get_all_param_values gives them")
+            init = list(init)
+        else:  # Lasagne's construction order: the first layer, the hidden layer, the output
+            init = [_glorot_uniform(F, C), np.zeros(C, np.float32)]
+            if K:
+                init += [_glorot_uniform(C, K), np.zeros(K, np.float32)]
+            init += [_glorot_uniform(K or C, V), np.zeros(V, np.float32)]
+        shapes = [(F, C), (C,)] + ([(C, K), (K,)] if K else []) + [(K or C, V), (V,)]
+        self.params = [self._param(x, s) for x, s in zip(init, shapes)]
+        self.Wg, self.bg = self.params[:2]
+        self.Wh, self.bh = (self.params[2], self.params[3]) if K else (None, None)
+        self.Wo, self.bo = self.params[-2], self.params[-1]
+        self._proj_h, self._proj_o = dense.Projection(), dense.Projection()
+        self.output_size = V
+        # one optimiser for every parameter: on a sparse input Wg's m and u are updated inside
+        # the one-pass step and the launches cover the others, on the same step count
+        self.optimizer = LasagneAdamax(self.params, lr=2e-3, beta1=0.9, beta2=0.999,
+                                       epsilon=1e-8)
+
+    def _first_layer(self, x, rows=None) -> torch.Tensor:
+        """rectify(X.Wg + bg) of the rows of x (every row, or the int32 device row ids `rows` of
+        a sparse x), in the padded layout the GEMMs take."""
+        if isinstance(x, gs.DeviceCSR):
+            return gs.spmm_rows(x, self.Wg, self.bg, rows, act="relu")
+        G = gs.empty_dense(x.shape[0], self.n_gaus_comp, self.device)
+        return G.copy_(torch.relu(torch.addmm(self.bg, x, self.Wg)))
+
+    def _to_coords(self, X, name: str = "X"):
+        """A model input on the device: a DeviceCSR for a sparse X, a float32 [n, input_size]
+        tensor for a dense one; the first input fixes an input_size left open."""
+        if sps.issparse(X) or isinstance(X, gs.DeviceCSR):
+            if self.input_size is None:
+                self.input_size = self.in_size = int(X.shape[1])
+            return self._input(X)
+        if isinstance(X, torch.Tensor):
+            X = X.detach().cpu().numpy()
+        X = np.asarray(X)
+        if X.ndim != 2:
+            raise ValueError(f"{name} must have shape (n, input_size), got {X.shape}")
+        if self.input_size is None:
+            self.input_size = self.in_size = int(X.shape[1])
+        if X.shape[1] != self.input_size:
+            raise ValueError(f"X has {X.shape[1]} columns, the model {self.input_size}")
+        return torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(self.device)
+
+    def _set_train(self, x) -> None:
+        self._sparse = isinstance(x, gs.DeviceCSR)
+        self._x_train = x
+        if not self._sparse:
+            self._train_data = x
+            return
+        # the rows are reached through their ids; every segmentation call is sized from the
+        # host's copy of indptr (copied once)
+        self._indptr_host = x.indptr.cpu().numpy().astype(np.int64)
+        self._train_data = torch.arange(x.n_rows, dtype=torch.int32, device=self.device)
+
+    def _plan_epoch(self, order: np.ndarray) -> np.ndarray:
+        if self._sparse:
+            return plan_segmented_epoch(self, order)
+        return super()._plan_epoch(order)
+
+    # -- training -----------------------------------------------------------------------
+    @torch.no_grad()
+    def _step(self, x, rows: torch.Tensor, seg=None, b: int = 0) -> torch.Tensor:
+        """One batch: x is the batch's [B, input_size] rows, or with `seg` (the run's
+        BatchSegments, b the batch's index in it) the sparse training input, `rows` its row ids.
+        The loss (device scalar), every gradient, then the Adamax update."""
+        B, opt = rows.numel(), self.optimizer
+        G = self._first_layer(x, rows if seg is not None else None)
+        H = G
+        if self.hid_size:
+            H = dense.gemm_nt(G, self._proj_h.fwd.get(self.Wh, True), bias=self.bh, act="relu")
+        Z = dense.gemm_nt(H, self._proj_o.fwd.get(self.Wo, True), bias=self.bo)
+        loss_rows, dZ = xent_csr_forward_backward(Z, self._y_train, rows, scale=1.0 / B,
+                                                  in_place=True)
+        loss = loss_rows.sum() / B
+        self.Wo.grad = dense.gemm_tn(H, dZ)
+        self.bo.grad = dZ.sum(dim=0) if dZ.shape[1] > 1024 else gs.colsum(dZ)
+        dH = dense.gemm_nt(dZ, self._proj_o.bwd.get(self.Wo, False))
+        if self.hid_size:
+            g, self.bh.grad = gs.relu_backward(dH, Y=H, out=dH)
+            self.Wh.grad = dense.gemm_tn(G, g)
+            dG = dense.gemm_nt(g, self._proj_h.bwd.get(self.Wh, False))
+        else:
+            dG = dH
+        gG, self.bg.grad = gs.relu_backward(dG, Y=G, out=dG)
+        if seg is None:
+            self.Wg.grad = x.t() @ gG
+            opt.step()
+            return loss
+        opt.prepare()
+        w1_adamax_step(self.Wg, opt.m[0], opt.u[0], gG, seg, b, opt.a_t, opt.beta1, opt.beta2,
+                       opt.eps)
+        opt.apply(first=1)
+        return loss
+
+    @torch.no_grad()
+    def _run_batches(self) -> torch.Tensor:
+        if not self._sparse:
+            return super()._run_batches()
+        B, X = self.batch_size, self._x_train
+        total = torch.zeros((), dtype=torch.float32, device=self.device)
+        self.batch_losses = []
+        for first, stop, nnz_sel in self._runs:
+            seg = BatchSegments(X, self._perm[first * B:stop * B], B, nnz_sel)
+            for b in range(first, stop):
+                # the order was checked on the host (a permutation of the training rows)
+                loss = self._step(X, self._perm[b * B:(b + 1) * B], seg, b - first)
+                self.batch_losses.append(loss)
+                total += loss
+        return total / self._n_batches
+
+    @torch.no_grad()
+    def gaus_output(self, X) -> np.ndarray:
+        """f_gaus (loc2lang.py:208): the first layer's output [n, n_gaus_comp], in row chunks."""
+        self._built()
+        x = self._to_coords(X)
+        n, step = x.shape[0], self._chunk_rows()
+        out = np.empty((n, self.n_gaus_comp), np.float32)
+        for a in range(0, n, step):
+            out[a:a + step] = self._first_layer(_row_chunk(x, a, min(a + step, n))).cpu().numpy()
+        return out
 
 
 NNModel = NNModel_loc2lang  # the reference's name for it

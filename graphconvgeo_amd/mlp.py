@@ -201,6 +201,31 @@ def w1_step(W: torch.Tensor, m: torch.Tensor, v: torch.Tensor, G: torch.Tensor,
     increment_version(v)
 
 
+def w1_adamax_step(W: torch.Tensor, m: torch.Tensor, u: torch.Tensor, G: torch.Tensor,
+                   seg: BatchSegments, b: int, a_t: torch.Tensor, beta1: float = 0.9,
+                   beta2: float = 0.999, eps: float = 1e-8) -> None:
+    """w1_step with the second update rule (gcg_minibatch_w1_adamax_step_f32): g = (X[batch])^T . G
+    with no penalty, then Lasagne Adamax (m, u) with the step size a_t (device scalar) -- the
+    sparse (grid) first layer of loc2lang's no-MDN baseline."""
+    for t, name in ((W, "W"), (m, "m"), (u, "u")):
+        gs._require_cuda(t, name)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != W.shape:
+            raise TypeError("w1_adamax_step needs contiguous float32 W, m, u of one shape")
+    F, K = W.shape
+    if G.dtype != torch.float32 or G.shape != (seg.batch, K) or (K > 1 and G.stride(1) != 1):
+        raise ValueError(f"G must be float32 [{seg.batch}, {K}] with unit column stride")
+    if not 0 <= b < seg.n_batches:
+        raise IndexError("batch index out of range")
+    with torch.cuda.device(W.device):
+        call("gcg_minibatch_w1_adamax_step_f32", F, K, _ptr(W), _ptr(m), _ptr(u), _ptr(G), _ld(G),
+             seg.batch, C.c_void_p(seg.batch_seg_ptr.data_ptr() + 4 * b), _ptr(seg.seg_col),
+             _ptr(seg.seg_ptr), _ptr(seg.ent_pos), _ptr(seg.ent_val), _ptr(a_t), float(beta1),
+             float(beta2), float(eps), _stream_handle(W.device))
+    increment_version(W)
+    increment_version(m)
+    increment_version(u)
+
+
 class MLP(MiniBatchTrainer):
     permutation_only = False  # the reference's order is one, but any in-range order trains
     _plan_epoch = plan_segmented_epoch

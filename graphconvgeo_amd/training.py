@@ -51,10 +51,11 @@ class LasagneOptimizer:
         self.a_t.fill_(self.step_size(self.t))
 
     @torch.no_grad()
-    def apply(self):
+    def apply(self, first: int = 0):
         """Device half of a step (capturable): one fused HIP launch per parameter instead of
-        ~8 elementwise torch kernels."""
-        for p, m, s in zip(self.params, self.m, getattr(self, self.second)):
+        ~8 elementwise torch kernels. first: the parameters before it are left to the caller (a
+        sparse-input weight updated, with its two states, inside its one-pass step)."""
+        for p, m, s in list(zip(self.params, self.m, getattr(self, self.second)))[first:]:
             g = p.grad.contiguous()
             if not p.is_contiguous():
                 raise ValueError(f"{type(self).__name__} needs contiguous parameters")

@@ -427,6 +427,23 @@ gcg_status gcg_minibatch_w1_step_f32(int64_t F, int64_t K, float* W, float* m, f
                                      gcg_stream_t stream);
 
 /*
+ * gcg_minibatch_w1_adamax_step_f32: the same pass with the second update rule, for the sparse
+ * (grid) first layer of loc2lang's no-MDN baseline, which trains with Adamax and no penalty:
+ *     d as above;  m, u, w updated as gcg_adamax_step_f32 does with g = d
+ * -- bitwise the composition of (X[batch])^T . G scattered into zeros and gcg_adamax_step_f32.
+ * Every row whose m is non-zero moves on every step, so the pass covers all of W here too. The
+ * kernel is gcg_minibatch_w1_step_f32's, instantiated on the rule; arguments and vector widths
+ * as there.
+ */
+gcg_status gcg_minibatch_w1_adamax_step_f32(int64_t F, int64_t K, float* W, float* m, float* u,
+                                            const float* G, int64_t ldg, int64_t batch,
+                                            const int32_t* seg_range, const int32_t* seg_col,
+                                            const int32_t* seg_ptr, const int32_t* ent_pos,
+                                            const float* ent_val, const float* step_dev,
+                                            float beta1, float beta2, float eps,
+                                            gcg_stream_t stream);
+
+/*
  * gcg_minibatch_segment_dropout: gcg_minibatch_segment with input dropout on X (the reference's
  * SparseInputDropoutLayer in front of a mini-batch trainer, lang2loc.py:280-281), the dropout
  * parameters of gcg_csr_dropout_f32 appended. Every selected entry is masked with the keep rule
@@ -1067,6 +1084,50 @@ gcg_status gcg_geo_eval_f64(int64_t M, const void* pred, int pred_is_int64, cons
                             int64_t C, const double* medians, double earth_radius_km,
                             double threshold_km, double* distance, int64_t* count_dev,
                             int32_t* status_dev, gcg_stream_t stream);
+
+/*
+ * The grid representation of loc2lang's no-MDN baseline (csrc/grid.hip; loc2lang.py:298-322):
+ * row i of an n x P CSR, P = n_lat * n_lon, holds an entry for every grid point nearer than
+ * radius_km to coords[i] (strict <), column i_lat * n_lon + i_lon ascending, with the value
+ * float32((1 / d) / sum of the row's 1 / d), d the distance of gcg_haversine_km_f64 -- float64
+ * throughout, one rounding at the store. When Z >= 1 columns lie at distance zero they hold 1 / Z
+ * and the row's other in-range columns an explicit +0.0 (the limit; the reference divides by
+ * zero). A row with no grid point in range is empty. coords: n x 2 [lat, lon] degrees; lats, lons:
+ * the grid's coordinate tables in degrees, ascending, as the host computed them (they are never
+ * re-derived from a start and a step); 2 * n_lat + n_lon <= 6144 (the tables live in LDS).
+ *
+ * gcg_grid_count_f64 writes indptr (int32[n + 1]; clamped at INT32_MAX), norm (float64[n]: the
+ * row's sum of 1 / d, or -Z) and info_dev (int64[2]: the total number of entries, summed in
+ * int64; 1 when a coordinate is not finite or |lat| > 90 -- such a row counts nothing and the
+ * result is to be dropped). The row sum adds the k-th entry of the row into slot k % 64 and folds
+ * the 64 slots by a fixed butterfly, so it depends on nothing but the row. gcg_grid_fill_f64,
+ * given the same arguments and count's indptr and norm, writes indices and values (nnz slots
+ * each; nnz = info_dev[0], which has to be below 2^31). One wave per coordinate.
+ *
+ * The window. A wave looks only at columns that can be in range, a superset by these bounds:
+ * d >= R |dlat|, so |dlat| < radius / R; and a >= cos(lat1) cos(lat2) sin^2(dlon / 2) with
+ * a < sin^2(radius / 2R), so inside a latitude row |sin(dlon / 2)| < sin(radius / 2R) /
+ * sqrt(cos(lat1) cos(lat2)) for dlon reduced to [-pi, pi] -- every longitude when that bound
+ * reaches 1 or the cosine product is 0 (near a pole). Both windows are widened by one cell, and
+ * the longitude window is taken around lon + 2 pi k for every k that reaches the table, lowest
+ * columns first. exhaustive = 1 makes the window the whole grid on the same code path; the
+ * results are bitwise the same.
+ *
+ * Asynchronous on `stream`, no allocation; n = 0 succeeds without a launch. The workspace
+ * (8-B aligned) is sized by gcg_grid_count_f64_workspace_bytes, which asks hipcub and so needs a
+ * HIP device for n > 0.
+ */
+gcg_status gcg_grid_count_f64_workspace_bytes(int64_t n, size_t* bytes);
+gcg_status gcg_grid_count_f64(int64_t n, const double* coords, int64_t n_lat, const double* lats,
+                              int64_t n_lon, const double* lons, double radius_km,
+                              double earth_radius_km, int exhaustive, int32_t* indptr,
+                              double* norm, int64_t* info_dev, void* workspace,
+                              size_t workspace_bytes, gcg_stream_t stream);
+gcg_status gcg_grid_fill_f64(int64_t n, const double* coords, int64_t n_lat, const double* lats,
+                             int64_t n_lon, const double* lons, double radius_km,
+                             double earth_radius_km, int exhaustive, const int32_t* indptr,
+                             const double* norm, int64_t nnz, int32_t* indices, float* values,
+                             gcg_stream_t stream);
 
 /*
  * k-means initialisation of the Gaussian components (csrc/kmeans.hip): get_cluster_centers of
