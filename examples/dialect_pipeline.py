@@ -5,6 +5,7 @@ synthetic tweets, with the training and the evaluation on the GPU:
   host  synthetic users in R regions; every region has planted words (its "DARE" entries) and
         one vocabulary entry with the region's name that co-occurs with the region
   GPU   mlp.MLP with a hidden layer, trained to predict the region from the bag of words
+        (--dropout: mlp.DropoutMLP, the reference's drop_out=True)
   GPU   get_embedding of the one-word-per-row matrix: a hidden-layer vector per word
   GPU   dialect.eval_embeddings: min-max + l1 scaling, the rank of every planted word among
         the neighbours of its region's entry, recall@k
@@ -56,15 +57,23 @@ def synthetic_problem(n_users=3000, regions=6, planted=40, vocab_size=3000, seed
     return X, region.astype(np.int64), vocab, {names[r]: set(words[r]) for r in range(regions)}
 
 
-def word_embeddings(X, region, vocab, hidden=64, epochs=8, batch=500, seed=7, as_tensor=True):
+def word_embeddings(X, region, vocab, hidden=64, epochs=8, batch=500, seed=7, as_tensor=True,
+                    dropout=False):
     """Train the MLP on 85 % of the users and return (model, the hidden-layer vector of every
-    vocabulary word): get_embedding of the V x V identity, one word per row."""
-    from graphconvgeo_amd.mlp import MLP
+    vocabulary word): get_embedding of the V x V identity, one word per row. dropout: the
+    trainer of main.py:425-427, MLP(..., drop_out=True, drop_out_coefs=[0.5, 0.5]) -- there with
+    hidden_layer_size=2048 (--hidden 2048)."""
+    from graphconvgeo_amd.mlp import MLP, DropoutMLP
 
     n_train = int(0.85 * X.shape[0])
-    np.random.seed(seed)  # the Glorot draws and the epoch shuffles come from numpy's stream
-    clf = MLP(n_epochs=epochs, batch_size=batch, hidden_layer_size=hidden, regul_coefs=(1e-6, 1e-6),
-              add_hidden=True)
+    # the Glorot draws, the dropout seeds and the epoch shuffles come from numpy's stream
+    np.random.seed(seed)
+    if dropout:
+        clf = DropoutMLP(n_epochs=epochs, batch_size=batch, hidden_layer_size=hidden,
+                         regul_coefs=(1e-6, 1e-6), add_hidden=True, drop_out_coefs=[0.5, 0.5])
+    else:
+        clf = MLP(n_epochs=epochs, batch_size=batch, hidden_layer_size=hidden,
+                  regul_coefs=(1e-6, 1e-6), add_hidden=True)
     clf.fit(X[:n_train], region[:n_train], X[n_train:], region[n_train:])
     one_word_per_row = sps.identity(len(vocab), dtype=np.float32, format="csr")
     return clf, clf.get_embedding(one_word_per_row, as_tensor=as_tensor), n_train
@@ -79,11 +88,15 @@ def main():
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--epochs", type=int, default=8)
     ap.add_argument("--nearest", type=int, default=8)
+    ap.add_argument("--dropout", action="store_true",
+                    help="train the embedding model with input dropout, as main.py:425-427 does "
+                         "(mlp.DropoutMLP)")
     args = ap.parse_args()
     from graphconvgeo_amd import dialect
 
     X, region, vocab, gold = synthetic_problem(args.users, args.regions, args.planted, args.vocab)
-    clf, embs, n_train = word_embeddings(X, region, vocab, args.hidden, args.epochs)
+    clf, embs, n_train = word_embeddings(X, region, vocab, args.hidden, args.epochs,
+                                         dropout=args.dropout)
     acc = clf.accuracy(X[n_train:], region[n_train:])
     lexicon = dialect.DialectLexicon(gold)
     ks = (args.planted, 2 * args.planted, 5 * args.planted)

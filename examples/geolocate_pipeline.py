@@ -18,6 +18,8 @@ the graph work and the training on the GPU:
   GPU   --device-mentions: mentions.mention_incidences_device finds the @mentions in the UTF-8
         bytes in HIP as well; the host looks each distinct name up once, and the incidences,
         the projected edges and H stay on the device
+  GPU   --text-classifier: main.py's main2 beside it, MLP(drop_out=True) on the features alone
+        (mlp.DropoutMLP, main.py:556-560)
 
 Synthetic data: users live in one of `regions`; they mention other users mostly from their
 own region and use region-specific words, so the graph and the text both carry the label.
@@ -79,6 +81,9 @@ def main():
                          "(tfidf.tokenize_corpus_device)")
     ap.add_argument("--device-mentions", action="store_true",
                     help="parse the @mentions on the GPU (mentions.mention_incidences_device)")
+    ap.add_argument("--text-classifier", action="store_true",
+                    help="also train main.py's text-only classifier (main2): mlp.DropoutMLP, the "
+                         "reference's MLP(drop_out=True), on the TF-IDF features")
     args = ap.parse_args()
     if args.device_tokenizer and not args.device_tfidf:
         ap.error("--device-tokenizer needs --device-tfidf")
@@ -140,6 +145,17 @@ def main():
     if args.device_tfidf:
         rec.update(tfidf="device", tfidf_s=round(t_tfidf, 3), tokenizer=vec.tokenizer,
                    tokenize_s=round(vec.tokenize_s_, 3))
+    if args.text_classifier:  # main.py's main2 (main.py:556-560): the text alone, with dropout
+        from graphconvgeo_amd.mlp import DropoutMLP
+
+        cut = (lambda a, b: X[a:b]) if sps.issparse(X) else X.row_slice
+        np.random.seed(77)  # the dropout seeds, the Glorot draws and the epoch shuffles
+        txt = DropoutMLP(n_epochs=args.epochs, batch_size=min(500, n_tr), regul_coefs=[1e-6, 1e-6],
+                         hidden_layer_size=args.hidden, drop_out_coefs=[0.5, 0.5],
+                         early_stopping_max_down=10)
+        txt.fit(cut(0, n_tr), Y[:n_tr], cut(n_tr, n_tr + n_dev), Y[n_tr:n_tr + n_dev])
+        rec.update(text_classifier_test_acc=round(
+            txt.accuracy(cut(n_tr + n_dev, len(Y)), Y[n_tr + n_dev:]), 4))
     if medians is not None:
         mean_km, median_km, acc161 = clf.geo_eval("test", locs[2], medians)
         rec.update(classes=int(regions), mean_km=round(mean_km, 3), median_km=round(median_km, 3),

@@ -61,6 +61,9 @@ SIGNATURES = {
     "gcg_dropout_relu_backward_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p,
                                                 C.c_size_t, C.c_uint32, C.c_float, C.c_uint64,
                                                 _p, C.c_uint32, _i64, _p]),
+    "gcg_rectify_backward_wide_f32": (C.c_int, [_i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p,
+                                                C.c_size_t, C.c_uint32, C.c_float, C.c_uint64,
+                                                _p, C.c_uint32, _i64, _p]),
     "gcg_csr_dropout_f32": (C.c_int, [_i64, _i64, _i64, _p, _p, _p, _p, C.c_int, C.c_uint32,
                                       C.c_float, C.c_uint64, _p, C.c_uint32, _p]),
     "gcg_spmm_plan_host": (C.c_int, [_i64, _p, _p, _i64, _i64, C.c_int, _p, _i64, _pi64, _p,

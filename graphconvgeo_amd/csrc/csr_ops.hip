@@ -161,6 +161,50 @@ __global__ __launch_bounds__(256) void dropout_relu_backward_kernel(
 #include "rectify_backward_pass.inc"
 }
 
+// The pass for any K (gcg_rectify_backward_wide_f32): the columns in slabs of kReluSlab, the slab
+// in blockIdx.y. A workgroup runs the included pass on its slab as on a matrix of that slab's
+// columns -- the names the pass reads (K, gY, g_out, gate, partial) are the slab's here -- so row
+// blocks, wave interleave, accumulation order and partials are the narrow kernels', which are
+// not touched. Slab s keeps its partials (one row of its own width per row block) behind those
+// of the slabs before it, all of full width: partial_all + n_blocks * kReluSlab * s.
+constexpr int kReluSlab = 64 * 4 * kReluMaxK4;
+
+// A slab's DropKey: the pass numbers a slab's columns from 0, the mask wants the logical column
+// kReluSlab * s + c. The pass calls drop_words / drop_element with its `d`; for this type they
+// resolve to the two overloads below, which add the slab's offset (a multiple of 4 columns).
+struct SlabDropKey : DropKey {
+  int col0;
+};
+
+__device__ __forceinline__ Philox4 drop_words(const SlabDropKey& d, int64_t i, int64_t j4) {
+  return drop_words(static_cast<const DropKey&>(d), i, j4 + (d.col0 >> 2));
+}
+
+__device__ __forceinline__ float drop_element(const SlabDropKey& d, int64_t i, int64_t j, float v) {
+  return drop_element(static_cast<const DropKey&>(d), i, j + d.col0, v);
+}
+
+template <int VEC, bool DROP, bool GATE>
+__global__ __launch_bounds__(256) void rectify_backward_wide_kernel(
+    int64_t M, int k_all, int64_t rows_per_block, const float* gY_all, int64_t ldg,
+    float* g_all, int64_t ldo, float* __restrict__ partial_all,
+    const uint8_t* __restrict__ gate_all, int64_t ldgate, DropKey key,
+    const int32_t* __restrict__ step_dev, int64_t row0) {
+  constexpr MaskSource kMask = GATE ? kMaskGate : kMaskNone;
+  constexpr bool kDrop = DROP;
+  const int col0 = static_cast<int>(blockIdx.y) * kReluSlab;
+  const int K = min(kReluSlab, k_all - col0);
+  const float* const gY = gY_all + col0;
+  float* const g_out = g_all + col0;
+  const uint8_t* const gate = GATE ? gate_all + col0 : nullptr;
+  float* const partial = partial_all + static_cast<int64_t>(gridDim.x) * col0;
+  const float* const Y = nullptr;  // (unread without kMaskY)
+  const int64_t ldy = 0;
+  SlabDropKey d{key, col0};  // (unread without kDrop)
+  if constexpr (DROP) d.step = static_cast<uint32_t>(*step_dev);
+#include "rectify_backward_pass.inc"
+}
+
 // out[c] = sum over the partial rows of partial[b][c], in a fixed order: workgroup = 16 waves
 // over 64 columns; wave w sums rows w, w + 16, ... in order, then wave 0 adds the 16 in order.
 __global__ __launch_bounds__(1024) void column_sum_kernel(int64_t n_blocks, int K,
@@ -524,7 +568,89 @@ gcg_status rectify_backward(const char* fn, MaskSource mask, const DropArgs* dro
   return GCG_OK;
 }
 
+// The host side of the pass in slabs (gcg_rectify_backward_wide_f32): rectify_backward's checks
+// without the K cap and without Y, one launch with the slab in gridDim.y, then column_sum_kernel
+// on every slab's partials.
+gcg_status rectify_backward_wide(const char* fn, const DropArgs* drop, int64_t M, int64_t K,
+                                 const float* gY, int64_t ldg, const uint8_t* gate,
+                                 int64_t ldgate, float* g_out, int64_t ldo, float* bias_grad,
+                                 void* workspace, size_t workspace_bytes, gcg_stream_t stream) {
+  // (at most 65535 slabs: gridDim.y)
+  if (M < 0 || K < 0 || K > int64_t{65535} * kReluSlab || (drop != nullptr && drop->row0 < 0))
+    return fail(GCG_ERR_INVALID_ARG, "%s: bad sizes M=%lld K=%lld", fn,
+                static_cast<long long>(M), static_cast<long long>(K));
+  if (gate == nullptr && drop == nullptr)
+    return fail(GCG_ERR_INVALID_ARG, "%s: neither gate nor dropout (gcg_column_sum_f32 sums)", fn);
+  auto st = static_cast<hipStream_t>(stream);
+  if (M == 0 || K == 0) {  // an empty sum is zero
+    if (bias_grad != nullptr && K > 0)
+      GCG_HIP_CHECK(hipMemsetAsync(bias_grad, 0, sizeof(float) * K, st));
+    return GCG_OK;
+  }
+  if (gY == nullptr || g_out == nullptr)
+    return fail(GCG_ERR_INVALID_ARG, "%s: null operand", fn);
+  if (ldg < K || ldo < K) return fail(GCG_ERR_INVALID_ARG, "%s: ld < K", fn);
+  if (gate != nullptr && (ldgate < K || ldgate % 4 != 0 || !aligned(gate, 4)))
+    return fail(GCG_ERR_MISALIGNED, "%s: gate needs ldgate >= K, ldgate %% 4 == 0, 4-B base", fn);
+  if (!aligned(gY, 4) || !aligned(g_out, 4) || (drop != nullptr && !aligned(drop->step_dev, 4)))
+    return fail(GCG_ERR_MISALIGNED, "%s: operand not 4-B aligned", fn);
+  const int64_t rpb = relu_rows_per_block(M);
+  const int64_t n_blocks = (M + rpb - 1) / rpb;
+  const size_t need = sizeof(float) * static_cast<size_t>(n_blocks) * K;
+  if (workspace == nullptr || workspace_bytes < need)  // the kernel always writes partials
+    return fail(GCG_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, need);
+  if (!aligned(workspace, 4)) return fail(GCG_ERR_MISALIGNED, "%s: workspace alignment", fn);
+  float* part = static_cast<float*>(workspace);
+  const bool vec = ldg % 4 == 0 && aligned(gY, 16) && ldo % 4 == 0 && aligned(g_out, 16);
+  if (!vec && K > 64 * kReluMaxK4)
+    return fail(GCG_ERR_MISALIGNED, "%s: K > %d needs 16-B rows (ld %% 4 == 0)", fn,
+                64 * kReluMaxK4);
+  const int64_t slabs = (K + kReluSlab - 1) / kReluSlab;
+  const dim3 grid(static_cast<unsigned>(n_blocks), static_cast<unsigned>(slabs));
+  const DropKey key = drop != nullptr ? drop->key : DropKey{};
+  const int32_t* step_dev = drop != nullptr ? drop->step_dev : nullptr;
+  const int64_t row0 = drop != nullptr ? drop->row0 : 0;
+#define GCG_WIDE_LAUNCH(V, D, G)                                                                \
+  hipLaunchKernelGGL((rectify_backward_wide_kernel<V, D, G>), grid, dim3(256), 0, st, M,        \
+                     int(K), rpb, gY, ldg, g_out, ldo, part, gate, ldgate, key, step_dev, row0)
+  const bool has_gate = gate != nullptr;
+  if (vec) {
+    if (drop == nullptr) { GCG_WIDE_LAUNCH(4, false, true); }
+    else if (has_gate) { GCG_WIDE_LAUNCH(4, true, true); }
+    else { GCG_WIDE_LAUNCH(4, true, false); }
+  } else {
+    if (drop == nullptr) { GCG_WIDE_LAUNCH(1, false, true); }
+    else if (has_gate) { GCG_WIDE_LAUNCH(1, true, true); }
+    else { GCG_WIDE_LAUNCH(1, true, false); }
+  }
+#undef GCG_WIDE_LAUNCH
+  GCG_HIP_CHECK(hipGetLastError());
+  if (bias_grad != nullptr)
+    for (int64_t s = 0; s < slabs; ++s) {
+      const int64_t c0 = s * kReluSlab, ks = std::min<int64_t>(kReluSlab, K - c0);
+      hipLaunchKernelGGL(column_sum_kernel, dim3(static_cast<unsigned>((ks + 63) / 64)),
+                         dim3(1024), 0, st, n_blocks, int(ks), part + n_blocks * c0,
+                         bias_grad + c0);
+      GCG_HIP_CHECK(hipGetLastError());
+    }
+  return GCG_OK;
+}
+
 }  // namespace
+
+gcg_status gcg_rectify_backward_wide_f32(int64_t M, int64_t K, const float* gY, int64_t ldg,
+                                         const uint8_t* gate, int64_t ldgate, float* g_out,
+                                         int64_t ldo, float* bias_grad, void* workspace,
+                                         size_t workspace_bytes, uint32_t threshold, float scale,
+                                         uint64_t seed, const int32_t* step_dev,
+                                         uint32_t stream_id, int64_t row0, gcg_stream_t stream) {
+  const DropArgs drop{{static_cast<uint32_t>(seed & 0xffffffffu),
+                       static_cast<uint32_t>(seed >> 32), 0u, stream_id, threshold, scale},
+                      step_dev, row0};
+  return rectify_backward_wide("gcg_rectify_backward_wide_f32",
+                               step_dev != nullptr ? &drop : nullptr, M, K, gY, ldg, gate, ldgate,
+                               g_out, ldo, bias_grad, workspace, workspace_bytes, stream);
+}
 
 gcg_status gcg_relu_backward_f32(int64_t M, int64_t K, const float* gY, int64_t ldg,
                                  const float* Y, int64_t ldy, float* g_out, int64_t ldo,

@@ -199,11 +199,10 @@ def dropout_relu_backward(gY: torch.Tensor, spec: DropoutSpec,
                           row0: int = 0):
     """(g, db): the gradient of drop(rectify(.)) and its column sums in one pass
     (gcg_dropout_relu_backward_f32): the mask is regenerated, then Theano's gate rule as
-    sparse.relu_backward(gate=...); gate None: g = keep ? gY * scale : 0. out may be gY."""
+    sparse.relu_backward(gate=...); gate None: g = keep ? gY * scale : 0. out may be gY.
+    Beyond 1024 columns the same pass in slabs of 1024 (gcg_rectify_backward_wide_f32)."""
     gs._require_cuda(gY, "gY")
     M, K = gY.shape
-    if K > 1024:
-        raise NotImplementedError("the fused dropout backward takes K <= 1024 columns")
     ldgate = 0
     if gate is not None:
         if gate.dtype != torch.uint8 or gate.shape != (M, K) or (K > 1 and gate.stride(1) != 1):
@@ -218,10 +217,11 @@ def dropout_relu_backward(gY: torch.Tensor, spec: DropoutSpec,
     _check_2d(out, "out")
     db = torch.empty(K, dtype=torch.float32, device=gY.device) if bias_grad else None
     ws = gs._colsum_workspace(M, K, gY.device)
+    ld = gs._ld16 if K > 256 else _ld
     with torch.cuda.device(gY.device):
-        call("gcg_dropout_relu_backward_f32", M, K, _ptr(gY), _ld(gY), _ptr(gate), ldgate,
-             _ptr(out), _ld(out), _ptr(db), _ptr(ws), ws.numel() * 4, *spec.abi(), int(row0),
-             _stream_handle(gY.device))
+        call("gcg_dropout_relu_backward_f32" if K <= 1024 else "gcg_rectify_backward_wide_f32",
+             M, K, _ptr(gY), ld(gY), _ptr(gate), ldgate, _ptr(out), ld(out), _ptr(db), _ptr(ws),
+             ws.numel() * 4, *spec.abi(), int(row0), _stream_handle(gY.device))
     return out, db
 
 
@@ -401,8 +401,8 @@ class _DenseDropout(torch.autograd.Function):
 
 
 class DropoutLayer(nn.Module):
-    """lasagne.layers.DropoutLayer on a dense [M, K] float32 tensor (K <= 1024): forward
-    gcg_dropout_f32, backward the mask regenerated by gcg_dropout_relu_backward_f32."""
+    """lasagne.layers.DropoutLayer on a dense [M, K] float32 tensor: forward gcg_dropout_f32,
+    backward the mask regenerated by dropout_relu_backward."""
 
     def __init__(self, incoming=None, p: float = 0.5, rescale: bool = True,
                  stream: Optional[DropoutStream] = None,
@@ -418,8 +418,8 @@ class DropoutLayer(nn.Module):
         if spec is None:
             return input
         _not_under_compile()
-        if input.dim() != 2 or input.shape[1] > 1024:
-            raise NotImplementedError("DropoutLayer takes a 2-D input of at most 1024 columns")
+        if input.dim() != 2:
+            raise NotImplementedError("DropoutLayer takes a 2-D input")
         return _DenseDropout.apply(input, spec)
 
     def get_output_for(self, input, **kwargs):

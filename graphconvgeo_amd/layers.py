@@ -198,8 +198,8 @@ def csr_matmul(A: gs.DeviceCSR, Z: torch.Tensor, bias: Optional[torch.Tensor] = 
     """Differentiable S.dot(A, Z) (+ bias, rectify, row subset) through the HIP kernels.
     Under torch.compile the registered op gcg::spmm_csr (graphconvgeo_amd.ops: same kernels,
     a fake kernel for tracing, its autograd formula made of gcg ops) stands in for the
-    autograd.Function. dropout: a dropout.DropoutSpec masks the output (eager only, at most
-    1024 columns: the fused backward's limit). gather_dtype="bfloat16" (eager only): Z, and in
+    autograd.Function. dropout: a dropout.DropoutSpec masks the output (eager only; its
+    backward is one pass at any width). gather_dtype="bfloat16" (eager only): Z, and in
     the backward the gradient, are rounded to bfloat16 once and gathered at half the bytes
     (GATHER_DTYPES above); the mask, the bias gradient and the rectify backward stay float32."""
     bf16 = _check_gather_dtype(gather_dtype) == "bfloat16"
@@ -208,13 +208,9 @@ def csr_matmul(A: gs.DeviceCSR, Z: torch.Tensor, bias: Optional[torch.Tensor] = 
             raise NotImplementedError(
                 "gather_dtype='bfloat16' is not available under torch.compile: the bf16-gather "
                 "kernels are not registered torch ops; run the layer eagerly")
-        if dropout is not None and Z.shape[1] > 1024:
-            raise NotImplementedError("output dropout takes at most 1024 columns")
         return _CSRMatMul.apply(Z, bias, A, act, rows, mode, dropout, True)
     if dropout is not None:
         _drop._not_under_compile()
-        if Z.shape[1] > 1024:
-            raise NotImplementedError("output dropout takes at most 1024 columns")
         return _CSRMatMul.apply(Z, bias, A, act, rows, mode, dropout)
     if torch.compiler.is_compiling():
         return _ops.spmm_csr(A, Z, bias, act, rows, mode)

@@ -24,7 +24,11 @@ mlp.py:272-285: strict acc_val > best_val_acc keeps the parameters, otherwise a 
 to early_stopping_max_down; the best parameters are restored (the last ones when no epoch ever
 improved -- the reference would crash on None there).
 
-Left out, as MLPCONV leaves them: complete_prob (soft labels), drop_out, dense inputs.
+DropoutMLP is the same trainer with the reference's drop_out=True: Philox masks on the input
+(applied where the epoch is segmented) and, as an option, on the hidden output.
+
+Left out, as MLPCONV leaves them: complete_prob (soft labels), dense inputs; with dropout also
+add_hidden=False.
 """
 from __future__ import annotations
 
@@ -37,6 +41,7 @@ import torch
 from torch.autograd.graph import increment_version
 
 from . import dense
+from . import dropout as _drop
 from . import sparse as gs
 from ._native import call
 from .layers import _as_device_csr, _glorot_uniform
@@ -238,7 +243,8 @@ class MLP(MiniBatchTrainer):
         if complete_prob:
             raise NotImplementedError("complete_prob (soft labels) is not built")
         if drop_out:
-            raise NotImplementedError("drop_out is not built for the mini-batch MLP")
+            raise NotImplementedError("MLP trains without dropout: drop_out=True is the class "
+                                      "DropoutMLP")
         if loss_name != "log":
             raise NotImplementedError("only the 'log' (categorical cross-entropy) loss is built")
         self.n_epochs = n_epochs
@@ -269,12 +275,16 @@ class MLP(MiniBatchTrainer):
             raise ValueError("init_parameters must be [W1, b1, W2, b2] (or [W, b] without a "
                              "hidden layer), as lasagne.layers.get_all_param_values gives them")
         param = self._param
-        # Lasagne GlorotUniform draws W1 then W2 from numpy's global stream, b = Constant(0.)
+        # Lasagne GlorotUniform draws W1 then W2 from numpy's global stream, b = Constant(0.);
+        # _construct_dropout: where the reference constructs a dropout layer (DropoutMLP draws
+        # its seed there, from the same stream)
+        self._construct_dropout("input")
         W1 = _glorot_uniform(in_size, K) if init is None else init[0]
         self.W1 = param(W1, (in_size, K))
         self.b1 = param(np.zeros(K, np.float32) if init is None else init[1], (K,))
         self.params = [self.W1, self.b1]
         if self.add_hidden:
+            self._construct_dropout("hidden")
             W2 = _glorot_uniform(K, out_size) if init is None else init[2]
             self.W2 = param(W2, (K, out_size)).requires_grad_(True)
             self.b2 = param(np.zeros(out_size, np.float32) if init is None else init[3],
@@ -288,6 +298,24 @@ class MLP(MiniBatchTrainer):
                                      epsilon=1e-8)
         self.m1 = torch.zeros_like(self.W1)
         self.v1 = torch.zeros_like(self.W1)
+
+    # -- what DropoutMLP adds: here, nothing -----------------------------------------------
+    def _construct_dropout(self, layer: str) -> None:
+        pass
+
+    def _segments(self, perm: torch.Tensor, nnz_sel: int):
+        """(segments, values) of a run of batches: the values stand in for X.data in the
+        forward (None: X's own)."""
+        return BatchSegments(self.Xd, perm, self.batch_size, nnz_sel), None
+
+    def _hidden_train(self, h: torch.Tensor, b: int) -> torch.Tensor:
+        """The hidden output of batch b of the epoch as the output layer is trained on it."""
+        return h
+
+    def _hidden_backward(self, g: torch.Tensor, gate):
+        """(g, db1) from the gradient of _hidden_train's output (gate None: no hidden
+        rectify)."""
+        return gs.epilogue_backward(g, gate, True)
 
     def _penalty_coefs(self):
         """(l1, l2) of W1 and of W2: 0.5 shares of the layer's regul_coef (mlp.py:216-224);
@@ -352,14 +380,15 @@ class MLP(MiniBatchTrainer):
         act = "relu" if self.add_hidden else None
         loss = acc = None
         for first, stop, nnz_sel in self._runs:
-            seg = BatchSegments(X, self._perm[first * B:stop * B], B, nnz_sel)
+            seg, vals = self._segments(self._perm[first * B:stop * B], nnz_sel)
             for b in range(first, stop):
                 rows = self._perm[b * B:(b + 1) * B]
                 y = self._epoch_data[b * B:(b + 1) * B]
                 last = b == self._n_batches - 1
                 gate = gs.empty_gate(B, K, dev) if self.add_hidden else None
                 # the order was range-checked on the host (plan_epoch)
-                h = gs.spmm_rows(X, self.W1, self.b1, rows, act=act, gate=gate)
+                h = gs.spmm_rows(X, self.W1, self.b1, rows, vals=vals, act=act, gate=gate)
+                h = self._hidden_train(h, b)
                 opt.zero_grad()
                 h.requires_grad_(True)
                 with torch.enable_grad():
@@ -371,7 +400,7 @@ class MLP(MiniBatchTrainer):
                 if last:  # the loss the reference reports: the last batch's, with the penalty
                     loss, acc = ce.detach() + self._penalty(), a
                 g = h.grad if h.grad.stride(-1) == 1 else h.grad.contiguous()
-                g, db1 = gs.epilogue_backward(g, gate, True)  # gate None: no hidden rectify
+                g, db1 = self._hidden_backward(g, gate)
                 opt.prepare()
                 if self._w1_update is not None:
                     self._w1_update(self, b, g, l1, l2)
@@ -443,3 +472,98 @@ class MLP(MiniBatchTrainer):
 
     def get_params(self):
         return [p.detach().cpu().numpy() for p in self.params]
+
+
+class DropoutMLP(MLP):
+    """MLP(drop_out=True, drop_out_coefs=[drop_out_hid, drop_out_in]) of the reference
+    (mlp.py:128, 164-183), as main.py trains its classifier (main.py:556-558) and its
+    dialect-embedding model (main.py:425-427, 2048 hidden units).
+
+    The input is dropped with p = drop_out_coefs[1] and Lasagne's rescale 1 / (1 - p). The
+    hidden dropout layer of mlp.py:179 is dead in the reference: it is bound to self.l_hid1,
+    while l_out is built on the local l_hid1, so nothing is dropped after the rectifier -- the
+    default here. hidden_dropout=True is this package's addition: p = drop_out_coefs[0] on the
+    rectified hidden output in training, what the line evidently meant and what MLPCONV does.
+    A coefficient of 0 means no mask for that layer. add_hidden=False is refused (the reference
+    fails there with a NameError on l_hid1, mlp.py:189-196).
+
+    Draws, in Lasagne's construction order from numpy's global stream: the input dropout's
+    seed, W1, the hidden dropout layer's seed (drawn whether or not hidden_dropout is on: the
+    reference constructs that layer), W2. init_parameters skips the two Glorot draws only.
+
+    Masks (dropout.DropoutStream; the step is the number of batches trained so far, across
+    segmentation runs and epochs): the input's on stream 0, keyed by (row id in X_train,
+    feature), applied where the epoch is segmented (BatchSegments); the hidden one on stream 1,
+    keyed by (position in the batch, hidden unit). Evaluation, prediction and get_embedding are
+    deterministic (mlp.py:201, 205) and inherited; the reported train loss and accuracy are the
+    last batch's from the masked forward (mlp.py:203, 210, 270)."""
+
+    # a row in two batches of a run would share one slot of the dropped values
+    permutation_only = True
+
+    def __init__(self, n_epochs=10, batch_size=1000, init_parameters=None, complete_prob=False,
+                 add_hidden=True, regul_coefs=(5e-5, 5e-5), save_results=False,
+                 hidden_layer_size=None, drop_out=True, drop_out_coefs=(0.5, 0.5),
+                 early_stopping_max_down=100000, loss_name="log", nonlinearity="rectify",
+                 device="cuda", hidden_dropout=False):
+        if not drop_out:
+            raise ValueError("DropoutMLP is the drop_out=True trainer; MLP trains without")
+        if not add_hidden:
+            raise ValueError("drop_out needs add_hidden=True (the reference fails without: "
+                             "mlp.py:189-196)")
+        super().__init__(n_epochs, batch_size, init_parameters, complete_prob, add_hidden,
+                         regul_coefs, save_results, hidden_layer_size, False, drop_out_coefs,
+                         early_stopping_max_down, loss_name, nonlinearity, device)
+        if len(self.drop_out_coefs) != 2:
+            raise ValueError("drop_out_coefs is [drop_out_hid, drop_out_in]")
+        for p in self.drop_out_coefs:
+            _drop.dropout_threshold(p)  # outside [0, 1): ValueError
+        self.drop_out = True
+        self.hidden_dropout = bool(hidden_dropout)
+
+    def _construct_dropout(self, layer: str) -> None:
+        p_hid, p_in = self.drop_out_coefs  # mlp.py:128
+        if layer == "input":
+            self.stream_in = _drop.DropoutStream(_drop.draw_seed(), 0, self.device)
+            self._drop_in = _drop.make_spec(self.stream_in, p_in)
+        else:
+            self.stream_hid = _drop.DropoutStream(_drop.draw_seed(), 1, self.device)
+            self._drop_hid = _drop.make_spec(self.stream_hid, p_hid) if self.hidden_dropout \
+                else None
+
+    def _segments(self, perm: torch.Tensor, nnz_sel: int):
+        if self._drop_in is None:
+            return super()._segments(perm, nnz_sel)
+        seg = BatchSegments(self.Xd, perm, self.batch_size, nnz_sel, self._drop_in,
+                            self._vals_drop)
+        return seg, self._vals_drop
+
+    def _hidden_train(self, h: torch.Tensor, b: int) -> torch.Tensor:
+        if self._drop_hid is None:
+            return h
+        self.stream_hid.set_step(self._steps_before + b)  # a device fill: no synchronisation
+        return _drop.dropout_dense(h, self._drop_hid, out=h)
+
+    def _hidden_backward(self, g: torch.Tensor, gate):
+        # the one-pass kernel at every width (epilogue_backward composes the unmasked rule in
+        # torch beyond 1024 columns)
+        if self._drop_hid is None:
+            return gs.relu_backward(g, gate=gate)
+        return _drop.dropout_relu_backward(g, self._drop_hid, gate=gate)
+
+    def _run_batches(self):
+        out = super()._run_batches()
+        self._steps_before += self._n_batches
+        return out
+
+    def fit(self, X_train, Y_train, X_dev, Y_dev, epoch_orders=None):
+        self._steps_before = 0  # batches trained before the current epoch: the masks' step
+        self._vals_drop = None
+        return super().fit(X_train, Y_train, X_dev, Y_dev, epoch_orders)
+
+    def _build(self, in_size: int, out_size: int):
+        super()._build(in_size, out_size)
+        # X's values behind the mask, once per fit: every batch's rows are rewritten by its
+        # segmentation call
+        if self._drop_in is not None:
+            self._vals_drop = torch.zeros_like(self.Xd.data)

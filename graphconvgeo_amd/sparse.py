@@ -654,6 +654,12 @@ def _ld(t: torch.Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
 
 
+def _ld16(t: torch.Tensor) -> int:
+    """_ld for the entries that want 16-B rows (ld % 4 == 0): a single row's width rounded up to
+    4 -- nothing is addressed through the stride of the only row."""
+    return t.stride(0) if t.shape[0] > 1 else max((t.shape[1] + 3) // 4 * 4, 1)
+
+
 def empty_dense(n: int, k: int, device, pad_to: int = 4) -> torch.Tensor:
     """[n, k] float32 view of an [n, ld] buffer, ld = row_stride(k) (pad_to = 4) or k rounded
     up to pad_to: rows 16-B aligned, so the kernels can use dwordx4 loads/stores whatever K
@@ -923,13 +929,15 @@ def column_sum(X: torch.Tensor) -> torch.Tensor:
     M, K = X.shape
     if K > 1 and X.stride(1) != 1:
         X = X.contiguous()
-    if K > 256 and M > 1 and (X.stride(0) % 4 or X.data_ptr() % 16):
+    if K > 256 and ((M > 1 and X.stride(0) % 4) or X.data_ptr() % 16):
         X = empty_dense(M, K, X.device).copy_(X)
     out = torch.empty(K, dtype=torch.float32, device=X.device)
     ws = _colsum_workspace(M, K, X.device)
     with torch.cuda.device(X.device):
-        call("gcg_column_sum_f32", M, K, _ptr(X), X.stride(0) if M > 1 else K, _ptr(out), _ptr(ws),
-             ws.numel() * 4, _stream_handle(X.device))
+        # (a single row wider than 256: its width rounded up to 4, or the entry refuses an odd K)
+        ldx = X.stride(0) if M > 1 else _ld16(X) if K > 256 else K
+        call("gcg_column_sum_f32", M, K, _ptr(X), ldx, _ptr(out), _ptr(ws), ws.numel() * 4,
+             _stream_handle(X.device))
     return out
 
 
@@ -938,7 +946,8 @@ def relu_backward(gY: torch.Tensor, Y: Optional[torch.Tensor] = None,
                   gate: Optional[torch.Tensor] = None):
     """(g, db) and db = column sums of g, one pass (the grad of rectify(. + b),
     mlpconv.py:75-77). With `gate` (the bytes spmm(gate=...) wrote): Theano's rule
-    g = gY, gY/2, 0 for a pre-activation > 0, == 0, < 0 (gcg_relu_backward_gate_f32);
+    g = gY, gY/2, 0 for a pre-activation > 0, == 0, < 0 (gcg_relu_backward_gate_f32, and beyond
+    its 1024 columns gcg_rectify_backward_wide_f32: the same pass on slabs of 1024 columns);
     with Y only: g = gY where Y > 0 else 0 (gcg_relu_backward_f32). out may be gY."""
     _require_cuda(gY, "gY")
     M, K = gY.shape
@@ -975,7 +984,11 @@ def relu_backward(gY: torch.Tensor, Y: Optional[torch.Tensor] = None,
         if K > 1 and t.stride(1) != 1:
             raise ValueError("relu_backward operands need unit column stride")
     with torch.cuda.device(gY.device):
-        if gate is not None:
+        if gate is not None and K > 1024:  # the same pass in slabs of 1024 columns, no mask
+            call("gcg_rectify_backward_wide_f32", M, K, _ptr(gY), _ld16(gY), _ptr(gate), ldgate,
+                 _ptr(out), _ld16(out), _ptr(db), _ptr(ws), ws.numel() * 4, 0, 1.0, 0, None, 0, 0,
+                 _stream_handle(gY.device))
+        elif gate is not None:
             call("gcg_relu_backward_gate_f32", M, K, _ptr(gY), ld(gY), _ptr(gate), ldgate,
                  _ptr(out), ld(out), _ptr(db), _ptr(ws), ws.numel() * 4, _stream_handle(gY.device))
         else:
@@ -995,9 +1008,10 @@ def epilogue_backward(gY: torch.Tensor, gate: Optional[torch.Tensor], want_bias:
     of the rule for the layers, the registered op and the trainers. gate: the rectify gate
     bytes of the forward (None: no rectify, g = gY); db = the column sums of g (None unless
     want_bias). drop (a dropout.DropoutSpec): the mask regenerated in the same pass
-    (dropout.dropout_relu_backward, at most 1024 columns). Up to 1024 columns the gate rule and
-    the sums are one kernel (relu_backward); beyond, Theano's 0.5 * g * (1 + sgn) from the gate
-    bytes (2 / 1 / 0) in torch."""
+    (dropout.dropout_relu_backward, any width). Without a mask, up to 1024 columns the gate rule
+    and the sums are one kernel (relu_backward); beyond, Theano's 0.5 * g * (1 + sgn) from the
+    gate bytes (2 / 1 / 0) in torch -- relu_backward(gate=...) takes those widths too, but its
+    column sums round in another order, so this branch keeps the bits its callers have."""
     if drop is not None:
         from . import dropout  # dropout imports this module
         return dropout.dropout_relu_backward(gY, drop, gate=gate, bias_grad=want_bias)

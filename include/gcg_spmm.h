@@ -327,6 +327,35 @@ gcg_status gcg_csr_dropout_f32(int64_t n_rows, int64_t n_cols, int64_t nnz,
                                gcg_stream_t stream);
 
 /*
+ * gcg_rectify_backward_wide_f32: the one pass of gcg_relu_backward_gate_f32 and
+ * gcg_dropout_relu_backward_f32 for any K (at most 65535 * 1024): the backward of a hidden
+ * layer wider than 1024 units. step_dev NULL: no mask (g = gY, gY/2, 0 by the gate byte; the
+ * other dropout arguments are ignored); step_dev given: t = keep ? fl32(gY * scale) : 0 first,
+ * and gate may then be NULL (g = t). Neither a gate nor a mask is GCG_ERR_INVALID_ARG: plain
+ * column sums are gcg_column_sum_f32's.
+ *
+ * The slab rule: the columns are cut into slabs of 1024, and slab s (columns 1024 s .. ) is
+ * processed exactly as the narrow entries process a matrix of that slab's columns -- the same
+ * row blocks, wave interleave, accumulation order and per-block partials, then the same final
+ * reduction -- with the mask of logical column 1024 s + c, i.e. the one gcg_dropout_f32 applied
+ * to the whole row. So g is what the rule above states element by element, and
+ * bias_grad[1024 s .. ] is bitwise gcg_column_sum_f32 of that slab of g. For K <= 1024 the
+ * results are bitwise the narrow entries'.
+ *
+ * Workspace: gcg_relu_backward_f32_workspace_bytes(M, K), required. Alignment as the narrow
+ * entries: 4-B bases; K > 256 needs 16-B aligned rows (16-B bases, ldg % 4 == 0, ldo % 4 == 0),
+ * else GCG_ERR_MISALIGNED; the gate a 4-B base and ldgate % 4 == 0. g_out may alias gY.
+ * M == 0 zeroes bias_grad.
+ */
+gcg_status gcg_rectify_backward_wide_f32(int64_t M, int64_t K, const float* gY, int64_t ldg,
+                                         const uint8_t* gate /*nullable*/, int64_t ldgate,
+                                         float* g_out, int64_t ldo,
+                                         float* bias_grad /*nullable*/, void* workspace,
+                                         size_t workspace_bytes, uint32_t threshold, float scale,
+                                         uint64_t seed, const int32_t* step_dev /*nullable*/,
+                                         uint32_t stream_id, int64_t row0, gcg_stream_t stream);
+
+/*
  * Column sums out[c] = sum_r X[r][c] (the bias gradient of a dense projection, colsum of the
  * logits gradient; Theano's grad of T.dot(h, W) + b, mlpconv.py:88-93), deterministic, same
  * kernels and workspace (gcg_relu_backward_f32_workspace_bytes) as gcg_relu_backward_f32.

@@ -13,6 +13,12 @@ the kernels the project had before it (one JSON line per measurement).
   segment   gcg_minibatch_segment over one epoch's batches (device events).
   epoch     one whole epoch of MLP at the config's size, the fused step against the same
             trainer stepping through the composition (host clock around a synchronise).
+  --dropout [--hidden-dropout] [--hidden K]
+            one whole epoch of DropoutMLP beside one of MLP, and the segmentation with and
+            without the input mask.
+  --only wide
+            the rectify / dropout backward at 500 x 2048 and 10000 x 2048
+            (gcg_rectify_backward_wide_f32) against the torch composition it stands in for.
 Every pair alternates A and B in one process; medians of --steps (>= 20) after --warmup.
 """
 from __future__ import annotations
@@ -193,6 +199,88 @@ def bench_epoch(dev, cfg, n_train, B, nnz_per_row, steps, warmup, seg_steps):
                       "ns_per_entry": round(med(ts) * 1e6 / max(nnz_sel, 1), 3)}), flush=True)
 
 
+def bench_dropout_epoch(dev, cfg, K, n_train, B, nnz_per_row, steps, warmup, hidden_dropout):
+    """--dropout: one epoch of DropoutMLP beside one of MLP (the same class the parent commit
+    has: its results are bitwise unchanged) on the same data, parameters and orders, alternated
+    in one process; host clock around a synchronise."""
+    F, Cn = cfg.n_features, cfg.n_classes
+    n_dev = 2 * B
+    X = synthetic_features(n_train + n_dev, F, nnz_per_row=nnz_per_row)
+    rng = np.random.default_rng(0)
+    Y = rng.integers(0, Cn, size=n_train + n_dev)
+    Y[:Cn] = np.arange(Cn)  # every class present: out_size = C
+    init = (glorot_uniform(F, K), np.zeros(K, np.float32), glorot_uniform(K, Cn, seed=3),
+            np.zeros(Cn, np.float32))
+    Xtr = gs.DeviceCSR.from_scipy(X[:n_train], dev)
+    Xdev = gs.DeviceCSR.from_scipy(X[n_train:], dev)
+    kw = dict(n_epochs=0, batch_size=B, hidden_layer_size=K, init_parameters=init,
+              regul_coefs=(1e-6, 1e-6), device=dev)
+    a = M.MLP(**kw).fit(Xtr, Y[:n_train], Xdev, Y[n_train:])
+    b = M.DropoutMLP(hidden_dropout=hidden_dropout, **kw).fit(Xtr, Y[:n_train], Xdev, Y[n_train:])
+    orders = [rng.permutation(n_train) for _ in range(warmup + steps)]
+    ta, tb = [], []
+    for i in range(warmup + steps):
+        x = (wall_ms(lambda: a._train_epoch(orders[i])), wall_ms(lambda: b._train_epoch(orders[i])))
+        if i >= warmup:
+            ta.append(x[0])
+            tb.append(x[1])
+    nb = M.n_batches(n_train, B)
+    nnz_sel = int(np.diff(X[:n_train].indptr)[orders[0][:nb * B]].sum())
+    perm = torch.from_numpy(orders[0][:nb * B].astype(np.int32)).to(dev)
+    seg_steps = max(steps, 5)
+    ts = [device_ms(lambda _i: M.BatchSegments(Xtr, perm, B, nnz_sel))
+          for _ in range(warmup + seg_steps)][warmup:]
+    td = [device_ms(lambda _i: M.BatchSegments(Xtr, perm, B, nnz_sel, b._drop_in, b._vals_drop))
+          for _ in range(warmup + seg_steps)][warmup:]
+    rec = {"metric": "mlp epoch with dropout, median ms", "config": cfg.name, "n_train": n_train,
+           "F": F, "K": K, "C": Cn, "B": B, "batches": nb, "entries": nnz_sel,
+           "hidden_dropout": bool(hidden_dropout), "steps": steps, "warmup": warmup,
+           "epoch_mlp_ms": med(ta), "epoch_dropout_ms": med(tb),
+           "ratio": round(med(tb) / med(ta), 3), "step_mlp_ms": round(med(ta) / nb, 4),
+           "step_dropout_ms": round(med(tb) / nb, 4), "segment_ms": med(ts),
+           "segment_dropout_ms": med(td),
+           "mask_ns_per_entry": round((med(td) - med(ts)) * 1e6 / max(nnz_sel, 1), 3)}
+    print(json.dumps(rec), flush=True)
+
+
+def bench_wide_backward(dev, Mr, K, steps, warmup, calls=20):
+    """--only wide: the hidden layer's backward beyond 1024 columns alone, device events around
+    `calls` back-to-back calls: gcg_rectify_backward_wide_f32 with the gate and with gate +
+    mask, against the torch composition of sparse.epilogue_backward (three elementwise passes, a
+    temporary and a sum) -- the only thing it can stand in for. Byte model: 9 B per element
+    (gradient in, gate in, gradient out); the operands are re-read every call, so up to the
+    Infinity Cache's size they may come from it."""
+    from graphconvgeo_amd import dropout as D
+
+    gY = gs.empty_dense(Mr, K, dev).normal_()
+    gate = gs.empty_gate(Mr, K, dev)
+    gate.copy_(torch.randint(0, 3, (Mr, K), device=dev, dtype=torch.uint8))
+    stream = D.DropoutStream(7, 1, dev)
+    stream.set_step(0)
+    spec = D.DropoutSpec(stream, 0.5)
+    legs = {"wide_gate": lambda _i: gs.relu_backward(gY, gate=gate),
+            "wide_gate_dropout": lambda _i: D.dropout_relu_backward(gY, spec, gate=gate),
+            "torch_composition": lambda _i: gs.epilogue_backward(gY, gate, True)}
+    g0, db0 = legs["wide_gate"](0)
+    g1, db1 = legs["torch_composition"](0)
+    t = {k: [] for k in legs}
+    for i in range(warmup + steps):
+        for k, fn in legs.items():
+            x = device_ms(fn, calls)
+            if i >= warmup:
+                t[k].append(x)
+    nbytes = 9 * Mr * K
+    rec = {"metric": "wide rectify backward, median ms", "M": Mr, "K": K, "steps": steps,
+           "warmup": warmup, "calls_per_sample": calls, "mbytes_model": round(nbytes / 1e6, 2),
+           "g_equal_to_composition": bool(torch.equal(g0, g1)),
+           "db_max_abs_diff_to_composition": float((db0 - db1).abs().max())}
+    for k, xs in t.items():
+        rec[k + "_ms"] = med(xs)
+        rec[k + "_gbps"] = round(nbytes / med(xs) / 1e6, 1)
+        rec[k + "_share_of_8tbps"] = round(nbytes / med(xs) / 1e6 / 8000.0, 4)
+    print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -203,12 +291,28 @@ def main():
     ap.add_argument("--train-rows", type=int, default=0,
                     help="training rows of the epoch (0: 60 %% of the config's nodes)")
     ap.add_argument("--batch", type=int, default=500)
-    ap.add_argument("--only", choices=["step", "epoch"], default=None)
+    ap.add_argument("--only", choices=["step", "epoch", "wide"], default=None)
+    ap.add_argument("--dropout", action="store_true",
+                    help="time the epoch and the step with DropoutMLP beside MLP")
+    ap.add_argument("--hidden-dropout", action="store_true",
+                    help="with --dropout: the hidden mask too")
+    ap.add_argument("--hidden", type=int, default=0,
+                    help="hidden units of the --dropout epoch (0: the config's)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_mlp.py measures on a HIP device; none is visible")
     dev = torch.device("cuda:0")
     B = args.batch
+    if args.only == "wide":  # the backward of a 2048-unit hidden layer at main.py's two batches
+        for rows in (500, 10000):
+            bench_wide_backward(dev, rows, 2048, args.steps, args.warmup)
+        return
+    if args.dropout or args.hidden_dropout:
+        cfg = CONFIGS[args.config]
+        n_train = args.train_rows or int(0.6 * cfg.n_nodes)
+        bench_dropout_epoch(dev, cfg, args.hidden or cfg.hidden, n_train, B, 64, args.epoch_steps,
+                            args.epoch_warmup, args.hidden_dropout)
+        return
     if args.only in (None, "step"):
         bench_step(dev, 10_000, 500, B, 64, args.steps, args.warmup)
         bench_step(dev, 50_000, 300, B, 64, args.steps, args.warmup)
